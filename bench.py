@@ -1,6 +1,7 @@
 """bench.py — batched BM25 CSC search throughput on MI355X (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2] [--full]
+                  [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
@@ -18,13 +19,25 @@ R-way replica job on one GPU).  ``--config c2`` (a 25.6 MB index, resident in th
 256 MB Infinity Cache) labels its roofline as effective bandwidth.
 
 Printed by rank 0: ONE JSON line with the metric (value = steps x Q / the
-barrier-bracketed wall time, max over ranks), the per-step median from HIP
-events, the roofline of the dominant kernel (the score pass, timed with HIP
-events on its stream over the timed region), the end-to-end host-buffer time
-(bm25_search: H2D queries -> D2H results, median of --e2e-batches, N=1) and
-the CPU baseline (the reference's scipy/numpy call sequence,
-oracle.search_faithful, on a seeded 64-query sample: one process, and a fork
-pool over the job's cores; rank 0 at N=1, run before the GPU is touched).
+barrier-bracketed wall time of the --steps timed steps, max over ranks;
+ms_per_step = that wall time / steps).  A plain run does only that: set up,
+warm up, time the steps, print the line.
+
+``--dump-outputs DIR`` writes what the last timed step returned — the [Q, k]
+doc ids (docs.npy, float64) and scores (scores.npy, float32) a caller of the
+timed search receives — after the timed steps (rank 0; at most 64 MB: a larger
+result is cut to a fixed seeded sample of its rows, rows.npy).  The inputs are
+seeded, so two builds run with the same arguments compare output for output.
+
+``--full`` adds to the line everything that takes work of its own: the
+per-step median from HIP events (the same steps again, an event between
+steps), the roofline of the dominant kernel (the score pass, timed with HIP
+events on its stream over the timed region, and one more search by the
+count_skips build), the end-to-end host-buffer time (bm25_search: H2D queries
+-> D2H results, median of --e2e-batches, N=1) and the CPU baseline (the
+reference's scipy/numpy call sequence, oracle.search_faithful, on a seeded
+64-query sample: one process, and a fork pool over the job's cores; rank 0 at
+N=1, run before the GPU is touched).
 """
 from __future__ import annotations
 
@@ -163,6 +176,34 @@ def cpu_baseline(args, n_docs, indptr, indices, data, queries, k):
                                      "note": f"EXTRAPOLATION: sample time x {Q}/sample"}}
 
 
+DUMP_LIMIT_BYTES = 64 * 2**20
+
+
+def dump_outputs(path: str, docs: np.ndarray, scores: np.ndarray,
+                 limit: int = DUMP_LIMIT_BYTES) -> dict:
+    """--dump-outputs: the [Q, k] result of the last timed step as
+    path/docs.npy (float64: doc ids up to 100M stay exact) and path/scores.npy
+    (float32, bit for bit).  A result over ``limit`` bytes is cut to a fixed
+    seeded sample of its rows, whose indices go to path/rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    Q, k = docs.shape
+    row_bytes = max(k, 1) * (8 + 4) + 8
+    rows = None
+    budget = limit - 1024  # the three .npy headers
+    if Q * row_bytes > budget:
+        keep = max(1, budget // row_bytes)
+        rows = np.sort(np.random.default_rng(20240601).permutation(Q)[:keep])
+        docs, scores = docs[rows], scores[rows]
+    np.save(os.path.join(path, "docs.npy"), docs.astype(np.float64))
+    np.save(os.path.join(path, "scores.npy"), np.ascontiguousarray(scores, dtype=np.float32))
+    rows_path = os.path.join(path, "rows.npy")
+    if rows is not None:
+        np.save(rows_path, rows.astype(np.float64))
+    elif os.path.exists(rows_path):  # of an earlier, larger dump into this directory
+        os.remove(rows_path)
+    return {"dir": path, "rows": int(docs.shape[0]), "of": int(Q), "k": int(k)}
+
+
 def launch_ranks(n: int) -> int:
     """`--gpus N` (N > 1) run without a launcher: start the N ranks as a
     child torch.distributed.run on 127.0.0.1 (this process has not touched
@@ -193,10 +234,18 @@ def main():
                     "runs one rank's doc shard, see --c5-rank); side lines: c3u (config 3 with "
                     "uniform weights: terms weigh alike), c3l (config 3's postings with "
                     "lucene scores: tf saturation and document lengths, built on the GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and report what a plain run leaves out: the CPU "
+                         "baseline (--cpu-queries), the per-step median, the roofline of the "
+                         "score pass and the end-to-end host-buffer time (--e2e-batches)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's [Q, k] result as "
+                         "DIR/docs.npy (float64) and DIR/scores.npy (float32); over 64 MB a "
+                         "fixed seeded sample of the rows (DIR/rows.npy)")
     ap.add_argument("--c5-rank", type=int, default=0,
                     help="config 5 at N=1: which of the 8 doc shards of the 8-GPU job to run")
     ap.add_argument("--cpu-queries", type=int, default=64,
-                    help="CPU baseline: seeded query sample size (0 = skip)")
+                    help="--full: CPU baseline's seeded query sample size (0 = skip)")
     ap.add_argument("--cpu-procs", type=int, default=-1,
                     help="CPU baseline pool leg: worker processes (default: the cgroup CPU "
                          "quota, 16 on the GPU box, else the affinity mask)")
@@ -206,8 +255,8 @@ def main():
     ap.add_argument("--k", type=int, default=0,
                     help="top-k (default: the config's); k > 4096 takes the large-k path")
     ap.add_argument("--e2e-batches", type=int, default=20,
-                    help="host-buffer searches (H2D queries -> D2H results) timed for the "
-                         "end-to-end median")
+                    help="--full: host-buffer searches (H2D queries -> D2H results) timed for "
+                         "the end-to-end median")
     ap.add_argument("--threads", type=int, default=16, help="host threads for index generation")
     ap.add_argument("--traffic", default=os.path.join(REPO, "profiles", "traffic.json"))
     ap.add_argument("--backend", default="nccl",
@@ -236,6 +285,9 @@ def main():
         sys.exit(launch_ranks(args.gpus))
     if args.replica_of > 1:
         args.mode = "replica"
+    if not args.full:  # a plain run: the timed steps and nothing beside them
+        args.cpu_queries = 0
+        args.e2e_batches = 0
 
     import torch
     from bm25mi import synth
@@ -332,7 +384,8 @@ def main():
     torch.cuda.synchronize(dev)
     if world > 1:
         dist.barrier()
-    index.profile_enable(True)
+    if args.full:  # the score pass's events, for the roofline
+        index.profile_enable(True)
     torch.cuda.synchronize(dev)
     if world > 1:
         dist.barrier()
@@ -343,22 +396,30 @@ def main():
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t_start
-    prof = index.profile_read()
     dispatch = index.last_dispatch()
-    stats = index.search_stats()  # the last timed search's selection counters
-    # per-step times for the median: the same steps again with an event
-    # between steps (every event record costs the device ~4 us, so not in the
-    # timed region above)
-    index.profile_enable(False)
-    evs = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
-    evs[0].record(stream)
-    for i in range(args.steps):
-        step()
-        evs[i + 1].record(stream)
-    torch.cuda.synchronize(dev)
-    if world > 1:
-        dist.barrier()
-    if info.get("tile_bounds") and (world == 1 or replica):
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the last timed step's result, before anything else searches
+        dumped = dump_outputs(args.dump_outputs, d_docs.cpu().numpy(), d_scores.cpu().numpy())
+        log(f"[rank 0] --dump-outputs: {dumped}")
+    prof = stats = step_ms = None
+    if args.full:
+        prof = index.profile_read()
+        stats = index.search_stats()  # the last timed search's selection counters
+        # per-step times for the median: the same steps again with an event
+        # between steps (every event record costs the device ~4 us, so not in
+        # the timed region above)
+        index.profile_enable(False)
+        evs = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+        evs[0].record(stream)
+        for i in range(args.steps):
+            step()
+            evs[i + 1].record(stream)
+        torch.cuda.synchronize(dev)
+        if world > 1:
+            dist.barrier()
+        step_ms = [evs[i].elapsed_time(evs[i + 1]) for i in range(args.steps)]
+    if args.full and info.get("tile_bounds") and (world == 1 or replica):
         # the (query, tile) pairs the tile bound skipped and their postings:
         # counted by the count_skips REST build (registers the timed build does
         # without), in one extra search of the same batch after the timed ones
@@ -371,7 +432,6 @@ def main():
         stats["bound_skipped_tiles"] = counted["bound_skipped_tiles"]
         stats["bound_skipped_postings"] = counted["bound_skipped_postings"]
         index.set_option("count_skips", 0)
-    step_ms = [evs[i].elapsed_time(evs[i + 1]) for i in range(args.steps)]
     # end-to-end (N=1): the host-buffer entry point bm25_search — H2D of the
     # query batch, the search, D2H of the [Q, k] results — timed per call
     e2e = None
@@ -405,27 +465,29 @@ def main():
 
     ms_per_step = 1000.0 * elapsed / max(args.steps, 1)
     qps = q_done * args.steps / elapsed
-    # roofline of the dominant kernel on this rank (rank 0 reports its own)
-    alg_bytes = algorithmic_bytes(indptr, queries, k)
-    kern_ms = prof["score_ms"] / max(prof["score_launches"], 1)
-    achieved = alg_bytes / (kern_ms * 1e-3) / 1e9
-    shift = int(np.log2(info["tile_docs"]))
-    default_k = cfg.k == synth.CONFIGS[args.config].k
-    traffic = (load_traffic(args.traffic, args.config, shift, T)
-               if world == 1 and not replica and default_k else None)
-    large_k = "large_k" in dispatch["kernels"]
-    # an index that fits the 256 MB Infinity Cache (MALL) is not HBM-bound:
-    # its rate is effective bandwidth over algorithmic bytes (config 2)
-    mall = info["device_bytes"] < 256 * 2**20
-    # the bytes beside the algorithmic ones: what the
-    # tile-bound skip spared (the kernel never reads those postings, so the
-    # algorithmic rate is partly an effective rate), the batch's distinct
-    # posting bytes (the reuse floor) and the counter-measured bytes
-    skip_post = max(0, int(stats.get("bound_skipped_postings", 0)))
-    n_post = query_postings(indptr, queries)
-    distinct = batch_distinct_postings(indptr, queries)
-    read_bytes = alg_bytes - 8 * skip_post
-    phys = (traffic.get("hbm_bytes_per_launch") / (kern_ms * 1e-3) / 1e9) if traffic else None
+    if args.full:
+        # roofline of the dominant kernel on this rank (rank 0 reports its own)
+        alg_bytes = algorithmic_bytes(indptr, queries, k)
+        kern_ms = prof["score_ms"] / max(prof["score_launches"], 1)
+        achieved = alg_bytes / (kern_ms * 1e-3) / 1e9
+        shift = int(np.log2(info["tile_docs"]))
+        default_k = cfg.k == synth.CONFIGS[args.config].k
+        traffic = (load_traffic(args.traffic, args.config, shift, T)
+                   if world == 1 and not replica and default_k else None)
+        large_k = "large_k" in dispatch["kernels"]
+        # an index that fits the 256 MB Infinity Cache (MALL) is not HBM-bound:
+        # its rate is effective bandwidth over algorithmic bytes (config 2)
+        mall = info["device_bytes"] < 256 * 2**20
+        # the bytes beside the algorithmic ones: what the
+        # tile-bound skip spared (the kernel never reads those postings, so the
+        # algorithmic rate is partly an effective rate), the batch's distinct
+        # posting bytes (the reuse floor) and the counter-measured bytes
+        skip_post = max(0, int(stats.get("bound_skipped_postings", 0)))
+        n_post = query_postings(indptr, queries)
+        distinct = batch_distinct_postings(indptr, queries)
+        read_bytes = alg_bytes - 8 * skip_post
+        phys = ((traffic.get("hbm_bytes_per_launch") / (kern_ms * 1e-3) / 1e9)
+                if traffic else None)
     from bm25mi import _capi
 
     if rank == 0:
@@ -443,7 +505,8 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": round(ms_per_step, 4),
-            "ms_per_step_median": round(float(np.median(step_ms)), 4),
+            "ms_per_step_median": round(float(np.median(step_ms)), 4) if args.full else None,
+            "full": args.full,
             "higher_is_better": True,
             "scaling": "strong",
             "native_lib": os.path.relpath(_capi.LIB, REPO),
@@ -472,7 +535,7 @@ def main():
                 "term_lanes": dispatch["term_lanes"],
                 "tiles_per_item": dispatch["band_tiles"],
             },
-            "roofline": {
+            "roofline": None if not args.full else {
                 "bound": "hbm",
                 "achieved": round(achieved, 1),
                 "peak": HBM_PEAK_GBPS,
@@ -524,6 +587,7 @@ def main():
             },
             "cpu_baseline": cpu,
             "e2e": e2e,
+            "outputs": dumped,
         }
         if cfg.k != synth.CONFIGS[args.config].k:  # a --k side line, not the config's metric
             out["metric"] = f"queries/sec, {args.config} index ({cfg.n_docs} docs) at k={cfg.k}"

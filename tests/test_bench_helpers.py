@@ -61,6 +61,35 @@ def test_posting_counts_per_query_and_batch_distinct():
     assert bench.batch_distinct_postings(indptr, np.full((2, 3), -1, np.int32)) == 0
 
 
+def test_dump_outputs_whole_and_sampled(tmp_path):
+    """--dump-outputs: docs (float64) and scores (float32) of the [Q, k]
+    result as .npy; over the size limit a fixed seeded sample of the rows,
+    the same from run to run, with their indices in rows.npy."""
+    rng = np.random.default_rng(3)
+    docs = rng.integers(0, 100_000_000, (37, 11)).astype(np.int32)
+    scores = rng.random((37, 11)).astype(np.float32)
+    d = str(tmp_path / "out")
+    big = str(tmp_path / "big")
+    info = bench.dump_outputs(d, docs, scores)
+    assert info["rows"] == info["of"] == 37 and sorted(os.listdir(d)) == ["docs.npy", "scores.npy"]
+    got_d, got_s = np.load(os.path.join(d, "docs.npy")), np.load(os.path.join(d, "scores.npy"))
+    assert got_d.dtype == np.float64 and np.array_equal(got_d, docs)
+    assert got_s.dtype == np.float32 and np.array_equal(got_s.view(np.uint32),
+                                                        scores.view(np.uint32))
+    limit = 1024 + 10 * (11 * 12 + 8)  # room for 10 of the 37 rows
+    for path in (big, d):  # a fresh directory, and over the earlier whole dump
+        info = bench.dump_outputs(path, docs, scores, limit=limit)
+        rows = np.load(os.path.join(path, "rows.npy")).astype(np.int64)
+        assert info["rows"] == len(rows) == 10 and np.all(np.diff(rows) > 0) and rows.max() < 37
+        assert np.array_equal(np.load(os.path.join(path, "docs.npy")), docs[rows])
+        assert np.array_equal(np.load(os.path.join(path, "scores.npy")), scores[rows])
+        assert sum(os.path.getsize(os.path.join(path, f)) for f in os.listdir(path)) <= limit
+    assert np.array_equal(np.load(os.path.join(big, "rows.npy")),
+                          np.load(os.path.join(d, "rows.npy")))
+    bench.dump_outputs(d, docs, scores)  # whole again: no stale rows.npy
+    assert not os.path.exists(os.path.join(d, "rows.npy"))
+
+
 def test_gpus_n_without_launcher_launches_ranks():
     """`bench.py --gpus 2` with no WORLD_SIZE starts the
     two ranks itself (a child torch.distributed.run on 127.0.0.1): the line
