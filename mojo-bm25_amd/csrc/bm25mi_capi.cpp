@@ -1168,6 +1168,7 @@ int bm25_scores_dense(bm25_index* h, const int32_t* query, int64_t T, float* out
   if (!h) return fail(BM25_EINVAL, "NULL index");
   if (T < 0) return fail(BM25_EINVAL, "negative query length");
   if (!out_scores) return fail(BM25_EINVAL, "NULL output");
+  if (T > 0 && !query) return fail(BM25_EINVAL, "NULL query");
   int64_t mx = 0;
   for (int64_t i = 0; i < T; ++i) mx = std::max<int64_t>(mx, query[i]);
   if (mx >= h->ix.n_terms)

@@ -236,3 +236,31 @@ def test_bm25_f64_one_document_corpus_is_pairwise():
         want = np.sum(v[None, :][:, ids], axis=1)
         got = oracle.scores_f64(1, ip, ix, v, ids)
         assert np.array_equal(got, want), T
+
+
+@pytest.mark.parametrize("N", [1, 2, 3, 8, 9, 64, 3000])
+def test_bm25_f64_scores_equal_numpy_sum_of_dense_matrix(N):
+    """oracle.scores_f64 against numpy itself, np.sum(m[:, ids], axis=1) on
+    the dense float64 matrix (bm25.py:143), bit for bit: signed values of
+    mixed magnitude (1e-8, 1, 1e8: the order of the adds shows), about 60 %
+    of the matrix filled, queries with duplicate ids.  Pins that only N = 1
+    is summed pairwise (every N >= 2 adds column by column, in query order)
+    and, at N = 1, every branch of _pairwise: fewer than 8 terms (in order),
+    blocks of 8 partial sums up to 128 terms (T = 8, 9, 127, 128) and the
+    halving recursion above 128 (T = 129, 300, 1000)."""
+    import scipy.sparse as sp
+    rng = np.random.default_rng(1000 + N)
+    V = 50
+    m = rng.uniform(-3.0, 3.0, (N, V)) * rng.choice([1e-8, 1.0, 1e8], (N, V))
+    m[rng.random((N, V)) >= 0.6] = 0.0
+    csc = sp.csc_matrix(m)
+    assert csc.has_canonical_format
+    ip, ix, d64 = csc.indptr.astype(np.int64), csc.indices.astype(np.int32), csc.data
+    for T in (0, 1, 7, 8, 9, 127, 128, 129, 300, 1000):
+        ids = rng.integers(0, V, T)
+        if T >= 7:
+            ids[T // 2] = ids[0]  # a duplicate even when T < V draws none
+        want = np.sum(m[:, ids], axis=1)
+        got = oracle.scores_f64(N, ip, ix, d64, ids)
+        assert got.dtype == np.float64 and got.shape == (N,)
+        assert np.array_equal(got.view(np.uint64), want.view(np.uint64)), (N, T)
