@@ -192,6 +192,44 @@ int bm25_scores_dense(bm25_index* idx, const int32_t* query, int64_t T,
                       float* out_scores);
 
 /*
+ * Scores of given (query, document) pairs: the candidates of a reranker, the
+ * documents another shard returned, a returned score to check.
+ * Replaces no reference call: BM25v.search is top-k only
+ * (bm25_native.py:76-158); this is the point lookup beside it.
+ *   queries    [Q, T] int32 as in bm25_search (negative = padding)
+ *   docs       [Q, C] int32 GLOBAL doc ids — the ids a search on this handle
+ *              returns, doc_offset included; negative = padding; a document
+ *              may appear several times in a row
+ *   out_scores [Q, C] f32
+ * out[q][c] is the fp32 sum, starting from +0.0f, over the valid token ids of
+ * query q in query order (a repeated id is added each time it occurs) of the
+ * index value of (term, docs[q][c]) where the document has that term: bit for
+ * bit bm25_scores_dense(queries[q])[docs[q][c] - doc_offset], and therefore the
+ * score bm25_search reports for that document.  Padding scores +0.0f (bits
+ * 0x00000000).
+ *   bm25_score_docs: host buffers, validated, synchronous; staged through
+ *     device buffers of the call's own on the handle's stream.  Q == 0 or
+ *     C == 0 returns BM25_OK without device work.
+ *     Errors: EINVAL when a token id >= n_terms (message matches
+ *     bm25_native.py:118-121, as bm25_search), when a non-negative doc id is
+ *     outside [doc_offset, doc_offset + n_docs) (the message names it), for
+ *     negative Q, T or C and NULL pointers with non-empty shapes.
+ *   bm25_score_docs_device: device buffers, enqueued on `stream`, validates
+ *     nothing and never synchronises.  Token ids >= n_terms are padding (as
+ *     bm25_search_device); doc ids outside the handle's range score +0.0f —
+ *     so doc shards add up: exactly one shard holds a document, the others
+ *     write +0.0f, and the element-wise fp32 sum of the shards' outputs is the
+ *     single-index output bit for bit.  It reads the immutable index arrays
+ *     only — not the search workspace — and is not ordered against the
+ *     handle's searches: it may run on its own stream while a search of the
+ *     same handle is in flight on another.
+ */
+int bm25_score_docs(bm25_index* idx, const int32_t* queries, int64_t Q, int64_t T,
+                    const int32_t* docs, int64_t C, float* out_scores);
+int bm25_score_docs_device(bm25_index* idx, const int32_t* d_queries, int64_t Q, int64_t T,
+                           const int32_t* d_docs, int64_t C, float* d_scores, void* stream);
+
+/*
  * bm25.BM25's float64 path (the dense model's API keeps the reference's
  * precision).  bm25_index_set_values_f64 keeps a float64 copy of the index's
  * values beside it (the same CSC order; bm25_build_scores method 1 returns

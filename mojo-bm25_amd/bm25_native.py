@@ -103,6 +103,29 @@ class BM25v:
         return self._compute_relevance_from_scores(queries=queries, top_k=top_k,
                                                    dtype=self.dtype)
 
+    def score(self, queries, docs) -> np.ndarray:
+        """Scores of given candidates (not in the reference, whose search is
+        top-k only): ``queries`` as for search, ``docs`` an int32 [Q, C] array
+        of doc ids (negative = padding, scored 0) -> float32 [Q, C]; each
+        score is the one search reports for that document."""
+        if len(queries) == 0:
+            return np.zeros((0, 0), dtype=self.dtype)
+        if (not isinstance(queries, np.ndarray) or queries.ndim != 2
+                or not isinstance(queries[0][0], TokId)):
+            raise ValueError("The queries must be a list of list of query token IDs.")
+        docs = np.asarray(docs)
+        if docs.ndim != 2 or docs.shape[0] != queries.shape[0]:
+            raise ValueError("docs must be a 2-D [Q, C] array with one row per query.")
+        max_token_id = int(queries.max(initial=0))
+        n_terms = self._gpu.n_terms if self._gpu is not None else len(self.doc_toks.indptr) - 1
+        if max_token_id >= n_terms:
+            raise ValueError(
+                f"The maximum token ID in the query ({max_token_id}) is higher than the number "
+                "of tokens in the index.")
+        if self._gpu is None:
+            raise ValueError("BM25v index not built. Call index() first.")
+        return self._gpu.score_docs(queries, docs)
+
     def _compute_relevance_from_scores(self, queries, top_k: int, dtype=np.float32):
         """bm25_native.py:129-158 on the GPU: per query, negative ids dropped,
         postings gathered, fp32 sums in query order, top-k."""

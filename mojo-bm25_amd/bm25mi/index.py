@@ -242,6 +242,45 @@ class GpuIndex:
         check(lib.bm25_scores_dense(self._h, _ptr(q), q.size, _ptr(out)))
         return out
 
+    # ------------------------------------------ given (query, document) pairs
+    def score_docs(self, queries, docs) -> np.ndarray:
+        """Scores of given candidates (bm25_score_docs, host arrays): queries
+        int32 [Q, T], docs int32 [Q, C] global doc ids (negative = padding)
+        -> float32 [Q, C], out[q, c] bit-equal to
+        ``scores_dense(queries[q])[docs[q, c] - doc_offset]``."""
+        q = np.ascontiguousarray(queries, dtype=np.int32)
+        d = np.ascontiguousarray(docs, dtype=np.int32)
+        if q.ndim != 2:
+            raise ValueError("queries must be a 2-D [Q, T] int32 array")
+        if d.ndim != 2:
+            raise ValueError("docs must be a 2-D [Q, C] int32 array")
+        if q.shape[0] != d.shape[0]:
+            raise ValueError(f"queries has {q.shape[0]} rows, docs has {d.shape[0]}")
+        out = np.zeros(d.shape, np.float32)
+        check(lib.bm25_score_docs(self._h, _ptr(q), q.shape[0], q.shape[1], _ptr(d), d.shape[1],
+                                  _ptr(out)))
+        return out
+
+    def score_docs_device(self, d_queries, d_docs, d_scores, stream=None) -> None:
+        """Device-resident score_docs (bm25_score_docs_device): torch int32
+        [Q, T] and [Q, C] in, float32 [Q, C] out, enqueued on ``stream`` with
+        no host synchronisation and no validation — token ids >= n_terms are
+        padding, doc ids outside this handle's range score +0.0 (doc shards'
+        outputs add up to the single-index output).  Reads the index arrays
+        only, so it may overlap a search of the same handle on another stream."""
+        if d_queries.dim() != 2 or d_docs.dim() != 2:
+            raise ValueError("d_queries and d_docs must be 2-D [Q, T] and [Q, C] tensors")
+        Q, T = d_queries.shape
+        if d_docs.shape[0] != Q:
+            raise ValueError(f"d_queries has {Q} rows, d_docs has {d_docs.shape[0]}")
+        C = d_docs.shape[1]
+        if d_scores.numel() != Q * C:
+            raise ValueError(f"d_scores must hold {Q} x {C} scores")
+        s = getattr(stream, "cuda_stream", stream) or 0
+        check(lib.bm25_score_docs_device(self._h, ctypes.c_void_p(d_queries.data_ptr()), Q, T,
+                                         ctypes.c_void_p(d_docs.data_ptr()), C,
+                                         ctypes.c_void_p(d_scores.data_ptr()), ctypes.c_void_p(s)))
+
     # ------------------------------------------- bm25.BM25's float64 path
     def set_values_f64(self, data64) -> None:
         """Keep a float64 copy of the values (same CSC order) on the device

@@ -1195,6 +1195,67 @@ int bm25_scores_dense(bm25_index* h, const int32_t* query, int64_t T, float* out
   return BM25_OK;
 }
 
+int bm25_score_docs(bm25_index* h, const int32_t* queries, int64_t Q, int64_t T,
+                    const int32_t* docs, int64_t C, float* out_scores) {
+  if (!h) return fail(BM25_EINVAL, "NULL index");
+  if (Q < 0 || T < 0 || C < 0) return fail(BM25_EINVAL, "negative query or candidate shape");
+  if (Q == 0 || C == 0) return BM25_OK;
+  if (T > 0 && !queries) return fail(BM25_EINVAL, "NULL queries");
+  if (!docs) return fail(BM25_EINVAL, "NULL docs");
+  if (!out_scores) return fail(BM25_EINVAL, "NULL output");
+  // bm25_native.py:116-121: max(initial=0) >= n_terms -> ValueError
+  int64_t mx = 0;
+  for (int64_t i = 0; i < Q * T; ++i) mx = std::max<int64_t>(mx, queries[i]);
+  if (mx >= h->ix.n_terms)
+    return fail(BM25_EINVAL,
+                "The maximum token ID in the query (%lld) is higher than the number of tokens in "
+                "the index.",
+                (long long)mx);
+  const int64_t lo = h->ix.doc_offset, hi = h->ix.doc_offset + h->ix.n_docs;
+  for (int64_t i = 0; i < Q * C; ++i)
+    if (docs[i] >= 0 && (docs[i] < lo || docs[i] >= hi))
+      return fail(BM25_EINVAL, "doc id %lld (row %lld) is outside the index's documents [%lld, %lld)",
+                  (long long)docs[i], (long long)(i / C), (long long)lo, (long long)hi);
+  std::lock_guard<std::mutex> lk(h->mu);
+  HIP_TRY(hipSetDevice(h->ix.device), "hipSetDevice");
+  // staging buffers of this call's own (as bm25_scores_dense): the search
+  // workspace and the search staging buffers stay untouched
+  int32_t* d_qq = nullptr;
+  int32_t* d_dd = nullptr;
+  float* d_out = nullptr;
+  hipError_t e = hipMalloc(&d_qq, sizeof(int32_t) * std::max<int64_t>(Q * T, 1));
+  if (e == hipSuccess) e = hipMalloc(&d_dd, sizeof(int32_t) * Q * C);
+  if (e == hipSuccess) e = hipMalloc(&d_out, sizeof(float) * Q * C);
+  if (e == hipSuccess && Q * T > 0)
+    e = hipMemcpyAsync(d_qq, queries, sizeof(int32_t) * Q * T, hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(d_dd, docs, sizeof(int32_t) * Q * C, hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) e = launch_score_docs(h->ix, d_qq, Q, T, d_dd, C, d_out, h->stream);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(out_scores, d_out, sizeof(float) * Q * C, hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  else hipStreamSynchronize(h->stream);  // (copies in flight read the caller's arrays)
+  hipFree(d_qq);
+  hipFree(d_dd);
+  hipFree(d_out);
+  if (e != hipSuccess) return hip_fail(e, "score_docs");
+  return BM25_OK;
+}
+
+int bm25_score_docs_device(bm25_index* h, const int32_t* d_queries, int64_t Q, int64_t T,
+                           const int32_t* d_docs, int64_t C, float* d_scores, void* stream) {
+  if (!h) return fail(BM25_EINVAL, "NULL index");
+  if (Q < 0 || T < 0 || C < 0) return fail(BM25_EINVAL, "negative query or candidate shape");
+  if (Q == 0 || C == 0) return BM25_OK;
+  // reads the immutable index arrays only: no workspace, no ordering against
+  // the handle's searches (ws_stream)
+  std::lock_guard<std::mutex> lk(h->mu);
+  HIP_TRY(hipSetDevice(h->ix.device), "hipSetDevice");
+  HIP_TRY(launch_score_docs(h->ix, d_queries, Q, T, d_docs, C, d_scores, (hipStream_t)stream),
+          "score_docs launch");
+  return BM25_OK;
+}
+
 int bm25_index_set_values_f64(bm25_index* h, const double* data64) {
   if (!h || (h->ix.nnz > 0 && !data64)) return fail(BM25_EINVAL, "NULL argument");
   if (!h->arrays) return fail(BM25_EINVAL, "unbuilt index");

@@ -314,6 +314,14 @@ hipError_t launch_select(const DevIndex& ix, const int32_t* d_queries,
                          int32_t* d_docs, float* d_scores, hipStream_t stream, bool unsorted = false);
 hipError_t launch_scores_dense(const DevIndex& ix, const int32_t* d_query,
                                int64_t T, float* d_out, hipStream_t stream);
+// Scores of given (query, document) pairs (bm25mi_lookup.hip): d_out[q * C + c]
+// = the fp32 sum, in query order from +0.0f, of the index values of
+// (d_queries[q][*], d_docs[q * C + c]) — element d_docs[..] - doc_offset of
+// launch_scores_dense's row.  d_docs holds global ids; a negative id or one
+// outside [doc_offset, doc_offset + n_docs) scores +0.0f.  Reads the index
+// arrays only (no workspace).
+hipError_t launch_score_docs(const DevIndex& ix, const int32_t* d_queries, int64_t Q, int64_t T,
+                             const int32_t* d_docs, int64_t C, float* d_out, hipStream_t stream);
 // W lists [Q, k] at element w * rank_stride (docs and scores alike) -> [Q, k];
 // sorted: every list is already best-first (W-way merge instead of a sort).
 hipError_t launch_merge_lists(const int32_t* d_docs, const float* d_scores,
