@@ -230,6 +230,72 @@ int bm25_score_docs_device(bm25_index* idx, const int32_t* d_queries, int64_t Q,
                            const int32_t* d_docs, int64_t C, float* d_scores, void* stream);
 
 /*
+ * Filtered search: the top-k among the documents an allow-mask lets through
+ * (a tenant, a date range, a language, "not deleted").
+ * Replaces no reference call: BM25v.search has no filter
+ * (bm25_native.py:76-158); the result is what its scorer and top-k give on
+ * the allowed documents alone.
+ *   queries    [Q, T] int32 as in bm25_search (negative = padding)
+ *   masks      [M, W] uint32, W = ceil(n_docs / 32), rows contiguous: document
+ *              doc_offset + d is allowed when bit d & 31 of word d >> 5 is set.
+ *              Bits are indexed by the handle's own documents (a doc shard
+ *              takes its slice of a collection's mask).  Bits at or past
+ *              n_docs in the last word are ignored and never produce a
+ *              document; no kernel reads a word at index >= W.
+ *   query_mask [Q] int32: query q uses mask query_mask[q] in [0, M); -1 = no
+ *              filter (the row equals bm25_search's bit for bit).  NULL = every
+ *              query uses mask 0.  M == 0 is valid only when every entry is -1.
+ *   out_docs / out_scores [Q, k]: row q = the first k of query q's allowed
+ *              documents by (fp32 score descending, doc id ascending); scores
+ *              are the bits bm25_scores_dense gives, ids are global.  Allowed
+ *              documents no query term touches are candidates at +0.0f, as in
+ *              bm25_search: an all-padding query returns its k smallest
+ *              allowed ids, and on an index with negative values zero-score
+ *              documents outrank negative ones.  Where fewer than k documents
+ *              are allowed the rest of the row is padding, doc -1 / score bits
+ *              0xFFFFFFFF — the padding of doc shards' lists, so the shards'
+ *              filtered lists merge through bm25_merge_topk_device unchanged.
+ *   0 <= k <= n_docs; k == 0 or Q == 0 returns BM25_OK without device work.
+ * k <= 4096 takes the tile passes (option filter_tiles): the best allowed
+ * keys of every tile — a tile without an allowed document reads no posting —
+ * their k-th as the threshold, the tiles that reach it scored again into
+ * per-query lists (capacity: option list_cap), sorted.  A query whose list
+ * overflows, every query of k > 4096 and every query when filter_tiles is 0
+ * take the dense path: dense score rows and a radix selection with the mask
+ * applied.  Every path gives the same bits.
+ *   bm25_search_filtered: host buffers, validated, synchronous.
+ *     Errors: EINVAL when a token id >= n_terms (message matches
+ *     bm25_native.py:118-121, as bm25_search), k out of range, a query_mask
+ *     entry outside [-1, M), negative shapes and NULL pointers with non-empty
+ *     shapes.
+ *   bm25_search_filtered_device: device buffers, enqueued on `stream`,
+ *     validates nothing (token ids >= n_terms are padding).  It is a search
+ *     of the handle: it takes the handle's mutex and uses its workspace,
+ *     ordered against the previous search's stream as bm25_search_device.  It
+ *     synchronises `stream` at most once per call, after the tile passes, to
+ *     count the queries handed to the dense path (as the large-k list path
+ *     does); a search served by the dense path alone never synchronises.  It
+ *     retains scratch with the handle, as the large-k path: 4 M (tiles + 1)
+ *     bytes for the census, and — only once queries took the dense path —
+ *     that path's chunk of score rows (4 B per document and query), at most
+ *     the large-k scratch budget (a quarter of the free device memory at
+ *     first use, at most 4 GiB).
+ */
+int bm25_search_filtered(bm25_index* idx, const int32_t* queries, int64_t Q, int64_t T, int32_t k,
+                         const uint32_t* masks, int64_t M, const int32_t* query_mask,
+                         int32_t* out_docs, float* out_scores);
+int bm25_search_filtered_device(bm25_index* idx, const int32_t* d_queries, int64_t Q, int64_t T,
+                                int32_t k, const uint32_t* d_masks, int64_t M,
+                                const int32_t* d_query_mask, int32_t* d_docs, float* d_scores,
+                                void* stream);
+/* Counters of the last filtered search, the first n (1..3) of:
+ *   [0] queries served by the dense path, [1] (query, tile) pairs pass A
+ *   skipped because the query's mask allows no document of the tile, [2]
+ *   (query, tile) pairs pass B scored again.
+ * Waits for the last search, like bm25_search_stats. */
+int bm25_search_filtered_stats(bm25_index* idx, int64_t* out, int32_t n);
+
+/*
  * bm25.BM25's float64 path (the dense model's API keeps the reference's
  * precision).  bm25_index_set_values_f64 keeps a float64 copy of the index's
  * values beside it (the same CSC order; bm25_build_scores method 1 returns
@@ -432,7 +498,7 @@ int bm25_search_counters(bm25_index* idx, int64_t* out, int32_t n);
  * environment (BM25_FLAT, BM25_FLAT_BW, BM25_ITEMS_PER_WAVE, BM25_SAMPLE_P,
  * BM25_LIST_CAP, BM25_CLAIM_CH, BM25_CLAIM_M, BM25_TILE_BOUND, BM25_THETA_BOUND,
  * BM25_GRID_PCT, BM25_LARGE_LISTS, BM25_COUNT_SKIPS, BM25_REST_SPLIT,
- * BM25_BOUND_POOL) at
+ * BM25_BOUND_POOL, BM25_FILTER_TILES) at
  * bm25_index_create; these
  * calls change or read them afterwards, effective from the next search.
  * Results never depend on them (every setting is bit-exact); they choose
@@ -484,6 +550,8 @@ int bm25_search_counters(bm25_index* idx, int64_t* out, int32_t n);
  *                    documents' scores) where there are >= 8k groups — a
  *                    quarter of the threshold kernel's bytes; 0: the per-tile
  *                    bounds
+ *   "filter_tiles"   1 (default): a filtered search of k <= 4096 takes the tile
+ *                    passes; 0: dense score rows for every query
  *   "grid_pct"       percent of the device's resident workgroup slots the
  *                    persistent score kernels launch (1..100, default 100):
  *                    below 100 leaves slots for kernels of another stream
@@ -506,7 +574,8 @@ int bm25_index_get_option(const bm25_index* idx, const char* name, int64_t* valu
  *                it is retried after 64, 128, ... 4096 searches; 512 (a
  *                flag): REST counted its skipped postings (count_skips);
  *                1024 (a flag): REST ran over split items (rest_split);
- *                2048 (a flag): the threshold read the pooled bounds (bound_pool)
+ *                2048 (a flag): the threshold read the pooled bounds (bound_pool);
+ *                4096: the filtered search's tile passes (its dense path sets 64)
  *   *term_lanes  flat kernel: term lanes per tile (8, 16, 32 or 64)
  *   band_tiles   [3]: flat kernel tiles per item of ALL, SAMPLE, REST
  *   *sample_p    sampling stride of the search (1: exact pass, 0: tile-bound

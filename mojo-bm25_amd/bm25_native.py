@@ -126,6 +126,37 @@ class BM25v:
             raise ValueError("BM25v index not built. Call index() first.")
         return self._gpu.score_docs(queries, docs)
 
+    def search_filtered(self, queries, top_k: int, allow) -> Tuple[np.ndarray, np.ndarray]:
+        """search restricted to the documents ``allow`` lets through (not in
+        the reference, whose search has no filter): ``allow`` is a bool
+        [n_docs] mask for every query, or [Q, n_docs] with one row per query
+        (packed uint32 rows of bm25mi.pack_mask work too).  Returns search's
+        tuple: doc ids (int32) and scores (f32), [Q, top_k]; rows with fewer
+        than top_k allowed documents end in doc -1 / NaN-bit scores."""
+        if len(queries) == 0:
+            return np.zeros((0, 0), dtype=self.dtype), np.zeros((0, 0), dtype=self.dtype)
+        if (not isinstance(queries, np.ndarray) or queries.ndim != 2
+                or not isinstance(queries[0][0], TokId)):
+            raise ValueError("The queries must be a list of list of query token IDs.")
+        allow = np.asarray(allow)
+        if allow.ndim not in (1, 2) or (allow.ndim == 2 and allow.shape[0] != queries.shape[0]):
+            raise ValueError("allow must be a [n_docs] mask or a [Q, n_docs] array with one "
+                             "row per query.")
+        if top_k < 0:
+            raise ValueError("negative dimensions are not allowed")
+        max_token_id = int(queries.max(initial=0))
+        n_terms = self._gpu.n_terms if self._gpu is not None else len(self.doc_toks.indptr) - 1
+        if max_token_id >= n_terms:
+            raise ValueError(
+                f"The maximum token ID in the query ({max_token_id}) is higher than the number "
+                "of tokens in the index.")
+        if self._gpu is None:
+            raise ValueError("BM25v index not built. Call index() first.")
+        if allow.ndim == 1:
+            return self._gpu.search_filtered(queries, top_k, allow)
+        return self._gpu.search_filtered(queries, top_k, allow,
+                                         np.arange(queries.shape[0], dtype=np.int32))
+
     def _compute_relevance_from_scores(self, queries, top_k: int, dtype=np.float32):
         """bm25_native.py:129-158 on the GPU: per query, negative ids dropped,
         postings gathered, fp32 sums in query order, top-k."""

@@ -19,6 +19,24 @@ def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
+def pack_mask(allow) -> np.ndarray:
+    """Allow-masks for the filtered search: bool [n_docs] or [M, n_docs] ->
+    uint32 [M, W], W = ceil(n_docs / 32), document d at bit d & 31 of word
+    d >> 5 (little bit order); the bits past n_docs are 0."""
+    a = np.asarray(allow)
+    if a.ndim == 1:
+        a = a[None, :]
+    if a.ndim != 2:
+        raise ValueError("allow must be a bool [n_docs] or [M, n_docs] array")
+    a = a.astype(bool)
+    M, n = a.shape
+    W = (n + 31) // 32
+    bits = np.zeros((M, W * 32), np.uint8)
+    bits[:, :n] = a
+    packed = np.packbits(bits, axis=1, bitorder="little")  # [M, 4 W] bytes, low byte first
+    return np.ascontiguousarray(packed).view("<u4").astype(np.uint32, copy=False).reshape(M, W)
+
+
 class GpuIndex:
     """A doc x term CSC score matrix resident in HBM.
 
@@ -281,6 +299,97 @@ class GpuIndex:
                                          ctypes.c_void_p(d_docs.data_ptr()), C,
                                          ctypes.c_void_p(d_scores.data_ptr()), ctypes.c_void_p(s)))
 
+    # ------------------------------------------------------- filtered search
+    def _masks_arg(self, masks) -> np.ndarray:
+        """bool [n_docs] / [M, n_docs] or packed uint32 [W] / [M, W] -> uint32
+        [M, W] for this index (shape errors raised here, before any C call)."""
+        m = np.asarray(masks)
+        W = (self.n_docs + 31) // 32
+        if m.dtype == np.bool_:
+            if m.ndim not in (1, 2) or m.shape[-1] != self.n_docs:
+                raise ValueError(f"a bool mask must have {self.n_docs} (n_docs) columns, "
+                                 f"got shape {m.shape}")
+            return pack_mask(m)
+        if m.dtype != np.uint32:
+            raise ValueError("masks must be bool [M, n_docs] or packed uint32 [M, W] "
+                             "(bm25mi.pack_mask)")
+        if m.ndim == 1:
+            m = m[None, :]
+        if m.ndim != 2 or m.shape[1] != W:
+            raise ValueError(f"packed masks must have {W} (ceil(n_docs / 32)) words per row, "
+                             f"got shape {m.shape}")
+        return np.ascontiguousarray(m)
+
+    def search_filtered(self, queries: np.ndarray, k: int, masks,
+                        query_mask=None) -> Tuple[np.ndarray, np.ndarray]:
+        """Top-k of every query among the documents its mask allows
+        (bm25_search_filtered, host arrays).  queries int32 [Q, T]; masks bool
+        [M, n_docs] (or [n_docs]) or packed uint32 [M, W] (pack_mask), bits by
+        this handle's own documents; query_mask int32 [Q] picks each query's
+        mask (-1: no filter; None: mask 0 for every query).  Rows with fewer
+        than k allowed documents end in padding (doc -1, score bits ~0)."""
+        q = np.ascontiguousarray(queries, dtype=np.int32)
+        if q.ndim != 2:
+            raise ValueError("queries must be a 2-D [Q, T] int32 array")
+        Q, T = q.shape
+        m = self._masks_arg(masks)
+        M = m.shape[0]
+        qm = None
+        if query_mask is not None:
+            qm = np.ascontiguousarray(query_mask, dtype=np.int32)
+            if qm.ndim != 1 or qm.size != Q:
+                raise ValueError(f"query_mask must hold one mask id per query ({Q}), "
+                                 f"got shape {qm.shape}")
+            if qm.size and (int(qm.min()) < -1 or int(qm.max()) >= M):
+                raise ValueError(f"query_mask entries must be in [-1, {M})")
+        elif M == 0 and Q > 0:
+            raise ValueError("no masks given: query_mask must be -1 for every query")
+        k = int(k)
+        docs = np.zeros((Q, max(k, 0)), np.int32)
+        scores = np.zeros((Q, max(k, 0)), np.float32)
+        check(lib.bm25_search_filtered(self._h, _ptr(q), Q, T, k, _ptr(m) if M else None, M,
+                                       _ptr(qm), _ptr(docs), _ptr(scores)))
+        return docs, scores
+
+    def search_filtered_device(self, d_queries, k: int, d_masks, d_query_mask, d_docs, d_scores,
+                               stream=None) -> None:
+        """Device-resident search_filtered (bm25_search_filtered_device): torch
+        int32 [Q, T] queries, packed masks [M, W] (int32 or uint32 storage),
+        int32 [Q] mask ids (or None: mask 0 for every query) in, int32 / float32
+        [Q, k] out, enqueued on ``stream``.  No validation: token ids >=
+        n_terms are padding and the mask ids must be in [-1, M).  It may
+        synchronise ``stream`` once, to count the queries whose candidate list
+        overflowed (they take the dense path)."""
+        if d_queries.dim() != 2:
+            raise ValueError("d_queries must be a 2-D [Q, T] tensor")
+        Q, T = d_queries.shape
+        W = (self.n_docs + 31) // 32
+        if d_masks.dim() != 2 or d_masks.shape[1] != W or d_masks.element_size() != 4:
+            raise ValueError(f"d_masks must be a packed [M, {W}] tensor of 32-bit words")
+        M = d_masks.shape[0]
+        if d_query_mask is not None and d_query_mask.numel() != Q:
+            raise ValueError(f"d_query_mask must hold one mask id per query ({Q})")
+        if d_query_mask is None and M == 0 and Q > 0:
+            raise ValueError("no masks given: d_query_mask must be -1 for every query")
+        k = int(k)
+        if d_docs.numel() != Q * k or d_scores.numel() != Q * k:
+            raise ValueError(f"d_docs and d_scores must hold {Q} x {k} results")
+        s = getattr(stream, "cuda_stream", stream) or 0
+        qm = None if d_query_mask is None else ctypes.c_void_p(d_query_mask.data_ptr())
+        check(lib.bm25_search_filtered_device(
+            self._h, ctypes.c_void_p(d_queries.data_ptr()), Q, T, k,
+            ctypes.c_void_p(d_masks.data_ptr()) if M else None, M, qm,
+            ctypes.c_void_p(d_docs.data_ptr()), ctypes.c_void_p(d_scores.data_ptr()),
+            ctypes.c_void_p(s)))
+
+    def filtered_stats(self) -> Tuple[int, int, int]:
+        """Counters of the last filtered search (bm25_search_filtered_stats):
+        queries served by the dense path, (query, tile) pairs pass A skipped
+        on an empty census, pairs pass B re-scored."""
+        v = (ctypes.c_int64 * 3)()
+        check(lib.bm25_search_filtered_stats(self._h, v, 3))
+        return int(v[0]), int(v[1]), int(v[2])
+
     # ------------------------------------------- bm25.BM25's float64 path
     def set_values_f64(self, data64) -> None:
         """Keep a float64 copy of the values (same CSC order) on the device
@@ -325,7 +434,7 @@ class GpuIndex:
     def set_option(self, name: str, value: int) -> None:
         """A search option of this handle (bm25_index_set_option: flat,
         flat_bw, items_per_wave, sample_p, list_cap, claim_ch, claim_m,
-        tile_bound, theta_bound).  In a multi-rank search every rank must
+        tile_bound, theta_bound, filter_tiles, ...).  In a multi-rank search every rank must
         change an option together (like a collective): the next
         ``bm25mi.dist.sharded_search`` re-checks the sample width they agree on."""
         check(lib.bm25_index_set_option(self._h, name.encode(), int(value)))
@@ -341,7 +450,7 @@ class GpuIndex:
     KERNELS = {1: "flat_sample", 2: "flat_rest", 4: "flat_all", 8: "wave_sample",
                16: "wave_rest", 32: "wave_all", 64: "large_k", 128: "bound_keys",
                256: "bound_off", 512: "count_skips", 1024: "rest_split",
-               2048: "bound_pool"}  # (flags, not
+               2048: "bound_pool", 4096: "filtered"}  # (flags, not
     # kernels: 256 the tile-bound threshold was off, 512 REST counted the postings it
     # skipped, 1024 REST ran over split items, 2048 the threshold read the pooled bounds)
 

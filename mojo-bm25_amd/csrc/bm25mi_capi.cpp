@@ -102,6 +102,7 @@ struct bm25_index {
   int64_t large_fallback = 0;  // queries of the last large-k list search taken by dense rows
                                // (-1: the dense path served the whole search)
   LargeArena arena;            // the large-k paths' scratch (grown to what they last asked for)
+  int64_t filtered_dense = 0;  // queries of the last filtered search the dense path served
 };
 
 namespace {
@@ -152,6 +153,7 @@ SearchOpts env_opts() {
   o.large_lists = env_int("BM25_LARGE_LISTS", o.large_lists) != 0;
   o.rest_split = env_int("BM25_REST_SPLIT", o.rest_split) != 0;
   o.bound_pool = env_int("BM25_BOUND_POOL", o.bound_pool) != 0;
+  o.filter_tiles = env_int("BM25_FILTER_TILES", o.filter_tiles) != 0;
   return o;
 }
 
@@ -196,6 +198,9 @@ int set_opt(SearchOpts& o, const char* name, int64_t v) {
   } else if (n == "bound_pool") {
     if (v != 0 && v != 1) return fail(BM25_EINVAL, "bound_pool must be 0 or 1");
     o.bound_pool = (int)v;
+  } else if (n == "filter_tiles") {
+    if (v != 0 && v != 1) return fail(BM25_EINVAL, "filter_tiles must be 0 or 1");
+    o.filter_tiles = (int)v;
   } else if (n == "count_skips") {
     if (v != 0 && v != 1) return fail(BM25_EINVAL, "count_skips must be 0 or 1");
     o.count_skips = (int)v;
@@ -225,6 +230,7 @@ int get_opt(const SearchOpts& o, const char* name, int64_t* v) {
   else if (n == "large_lists") *v = o.large_lists;
   else if (n == "rest_split") *v = o.rest_split;
   else if (n == "bound_pool") *v = o.bound_pool;
+  else if (n == "filter_tiles") *v = o.filter_tiles;
   else return fail(BM25_EINVAL, "unknown option '%s'", name);
   return BM25_OK;
 }
@@ -496,6 +502,48 @@ int run_search(bm25_index* h, const int32_t* d_queries, int64_t Q, int64_t T, in
   HIP_TRY(launch_select(h->ix, d_queries, Q, T, k, P, h->ws, d_docs, d_scores, st, shard),
           "select launch");
   HIP_TRY(record_end(h, ev, st), "hipEventRecord");
+  if (h->prof) {
+    h->score_launches += 1;
+    h->searches += 1;
+  }
+  return BM25_OK;
+}
+
+// The filtered search's device pipeline on stream st (bm25mi_filter.hip);
+// caller holds h->mu and has set the device.  A search of the handle: the
+// workspace, its stream ordering and the large-k scratch as run_search's.
+int run_filtered(bm25_index* h, const int32_t* d_queries, int64_t Q, int64_t T, int k,
+                 const uint32_t* d_masks, int64_t M, const int32_t* d_query_mask, int32_t* d_docs,
+                 float* d_scores, hipStream_t st) {
+  if (Q == 0 || k == 0) return BM25_OK;
+  const int rc = ensure_ws(h, Q, T, std::min<int>(k, kMaxK), st);
+  if (rc) return rc;
+  if (h->arena.need > h->arena.bytes) {
+    if (h->ws_stream) HIP_TRY(hipStreamSynchronize(h->ws_stream), "hipStreamSynchronize");
+    hipFree(h->arena.base);
+    h->arena.base = nullptr;
+    h->arena.bytes = 0;
+    HIP_TRY(hipMalloc((void**)&h->arena.base, h->arena.need), "hipMalloc(filtered scratch)");
+    h->arena.bytes = h->arena.need;
+  }
+  h->arena.used = 0;
+  h->ws.arena = &h->arena;
+  HIP_TRY(order_ws(h, st), "workspace order");
+  h->large_fallback = 0;
+  h->ix.disp = Dispatch{};
+  h->ix.disp.sample_p = 1;
+  h->ws.report = nullptr;
+  EventPair* ev = next_events(h);
+  if (ev) HIP_TRY(hipEventRecord(ev->a, st), "hipEventRecord");
+  int64_t nd = 0;
+  HIP_TRY(launch_search_filtered(h->ix, d_queries, Q, T, k, d_masks, M, d_query_mask, h->ws,
+                                 d_docs, d_scores, &nd, st),
+          "filtered search");
+  h->filtered_dense = nd;
+  if (ev) {
+    HIP_TRY(hipEventRecord(ev->b, st), "hipEventRecord");
+    HIP_TRY(record_end(h, ev, st), "hipEventRecord");
+  }
   if (h->prof) {
     h->score_launches += 1;
     h->searches += 1;
@@ -837,6 +885,102 @@ int bm25_search_device(bm25_index* h, const int32_t* d_queries, int64_t Q, int64
   std::lock_guard<std::mutex> lk(h->mu);
   HIP_TRY(hipSetDevice(h->ix.device), "hipSetDevice");
   return run_search(h, d_queries, Q, T, k, d_docs, d_scores, (hipStream_t)stream);
+}
+
+int bm25_search_filtered(bm25_index* h, const int32_t* queries, int64_t Q, int64_t T, int32_t k,
+                         const uint32_t* masks, int64_t M, const int32_t* query_mask,
+                         int32_t* out_docs, float* out_scores) {
+  if (!h) return fail(BM25_EINVAL, "NULL index");
+  if (Q < 0 || T < 0 || M < 0) return fail(BM25_EINVAL, "negative query or mask shape");
+  int rc = check_k(h, k);
+  if (rc) return rc;
+  if (Q == 0 || k == 0) return BM25_OK;
+  if (T > 0 && !queries) return fail(BM25_EINVAL, "NULL queries");
+  if (M > 0 && !masks) return fail(BM25_EINVAL, "NULL masks");
+  if (M == 0 && !query_mask)
+    return fail(BM25_EINVAL, "no masks: query_mask must name -1 (no filter) for every query");
+  if (!out_docs || !out_scores) return fail(BM25_EINVAL, "NULL output");
+  // bm25_native.py:116-121: max(initial=0) >= n_terms -> ValueError
+  int64_t mx = 0;
+  for (int64_t i = 0; i < Q * T; ++i) mx = std::max<int64_t>(mx, queries[i]);
+  if (mx >= h->ix.n_terms)
+    return fail(BM25_EINVAL,
+                "The maximum token ID in the query (%lld) is higher than the number of tokens in "
+                "the index.",
+                (long long)mx);
+  if (query_mask)
+    for (int64_t i = 0; i < Q; ++i)
+      if (query_mask[i] < -1 || query_mask[i] >= M)
+        return fail(BM25_EINVAL, "query_mask[%lld] = %d is outside [-1, %lld)", (long long)i,
+                    query_mask[i], (long long)M);
+  std::lock_guard<std::mutex> lk(h->mu);
+  HIP_TRY(hipSetDevice(h->ix.device), "hipSetDevice");
+  rc = ensure_io(h, Q * T, Q * (int64_t)k);
+  if (rc) return rc;
+  // the masks and mask ids: staging buffers of this call's own
+  const int64_t W = (h->ix.n_docs + 31) >> 5;
+  uint32_t* d_masks = nullptr;
+  int32_t* d_qm = nullptr;
+  hipError_t e = hipSuccess;
+  if (M > 0) e = hipMalloc(&d_masks, sizeof(uint32_t) * M * W);
+  if (e == hipSuccess && query_mask) e = hipMalloc(&d_qm, sizeof(int32_t) * Q);
+  if (e == hipSuccess && M > 0)
+    e = hipMemcpyAsync(d_masks, masks, sizeof(uint32_t) * M * W, hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess && query_mask)
+    e = hipMemcpyAsync(d_qm, query_mask, sizeof(int32_t) * Q, hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess && Q * T > 0)
+    e = hipMemcpyAsync(h->d_q, queries, sizeof(int32_t) * Q * T, hipMemcpyHostToDevice, h->stream);
+  if (e != hipSuccess) {
+    hipStreamSynchronize(h->stream);  // (copies in flight read the caller's arrays)
+    hipFree(d_masks);
+    hipFree(d_qm);
+    return hip_fail(e, "filtered search staging");
+  }
+  rc = run_filtered(h, h->d_q, Q, T, k, d_masks, M, d_qm, h->d_docs, h->d_scores, h->stream);
+  if (rc == BM25_OK) {
+    e = hipMemcpyAsync(out_docs, h->d_docs, sizeof(int32_t) * Q * k, hipMemcpyDeviceToHost,
+                       h->stream);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(out_scores, h->d_scores, sizeof(float) * Q * k, hipMemcpyDeviceToHost,
+                         h->stream);
+  }
+  const hipError_t es = hipStreamSynchronize(h->stream);
+  hipFree(d_masks);
+  hipFree(d_qm);
+  if (rc) return rc;
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) return hip_fail(e, "filtered search");
+  return BM25_OK;
+}
+
+int bm25_search_filtered_device(bm25_index* h, const int32_t* d_queries, int64_t Q, int64_t T,
+                                int32_t k, const uint32_t* d_masks, int64_t M,
+                                const int32_t* d_query_mask, int32_t* d_docs, float* d_scores,
+                                void* stream) {
+  if (!h) return fail(BM25_EINVAL, "NULL index");
+  if (Q < 0 || T < 0 || M < 0) return fail(BM25_EINVAL, "negative query or mask shape");
+  int rc = check_k(h, k);
+  if (rc) return rc;
+  if (Q == 0 || k == 0) return BM25_OK;
+  std::lock_guard<std::mutex> lk(h->mu);
+  HIP_TRY(hipSetDevice(h->ix.device), "hipSetDevice");
+  return run_filtered(h, d_queries, Q, T, k, d_masks, M, d_query_mask, d_docs, d_scores,
+                      (hipStream_t)stream);
+}
+
+int bm25_search_filtered_stats(bm25_index* h, int64_t* out, int32_t n) {
+  if (!h) return fail(BM25_EINVAL, "NULL index");
+  if (!out) return fail(BM25_EINVAL, "NULL argument");
+  if (n < 1 || n > 3) return fail(BM25_EINVAL, "n=%d must be in 1..3", n);
+  std::lock_guard<std::mutex> lk(h->mu);
+  HIP_TRY(hipSetDevice(h->ix.device), "hipSetDevice");
+  int32_t cnt[kCounters] = {};
+  read_counters(h, cnt);
+  // (counters [5] and [3]: pass A's skipped pairs, pass B's re-scored pairs)
+  const bool tiles = (h->ix.disp.kernels & kKFiltered) != 0;
+  const int64_t v[3] = {h->filtered_dense, tiles ? cnt[5] : 0, tiles ? cnt[3] : 0};
+  for (int i = 0; i < n; ++i) out[i] = v[i];
+  return BM25_OK;
 }
 
 int bm25_index_bounds_export(bm25_index* h, uint16_t* d_out, int64_t stride, void* stream) {

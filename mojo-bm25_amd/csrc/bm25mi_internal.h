@@ -16,6 +16,9 @@
 #include <stdint.h>
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <vector>
+
 namespace bm25mi {
 
 // Candidate key: (sortable f32 score bits) << 32 | (0xFFFFFFFF - doc).
@@ -85,6 +88,8 @@ struct SearchOpts {
   int rest_split = 0;      // REST over split items where the waves get few items (measured: no gain)
   int bound_pool = 1;      // the tile-bound threshold from the pooled bounds (bpool / wbpool) where
                            // they hold >= kPoolGroupsPerK * k groups
+  int filter_tiles = 1;    // filtered search, k <= kMaxK: the tile passes (0: dense score rows
+                           // for every query)
 };
 
 // What the last search launched (bm25_search_dispatch).
@@ -98,6 +103,7 @@ enum {
   kKCountSkips = 512,  // (a flag) REST counted the postings its tile bound skipped
   kKRestSplit = 1024,  // (a flag) REST ran over split items (heavy queries' bands in pieces)
   kKBoundPool = 2048,  // (a flag) the tile-bound threshold came from the pooled bounds
+  kKFiltered = 4096,   // the filtered search's tile passes (bm25mi_filter.hip)
 };
 struct Dispatch {
   uint32_t kernels = 0;       // kK* bits of the score kernels launched
@@ -179,6 +185,48 @@ struct LargeArena {
   size_t used = 0;     // bump offset of the live scratch users
   size_t need = 0;     // the most the last searches asked for
   int64_t budget = 0;  // bytes one search may take (large_budget(), fixed at first use)
+};
+
+// Scratch of one launch sequence.  With a handle's arena (LargeArena) the
+// buffers come from it; what does not fit is allocated stream-ordered,
+// released on `st` after everything enqueued so far, and counted, so the host
+// grows the arena before the handle's next search: a large-k search then
+// allocates nothing (each stream-ordered allocation and free cost the host
+// ~0.1 ms: ~2 ms per search at c3, k = 10 000, before its first kernel).  The
+// device's default pool keeps its default release threshold (the process's
+// other users of the pool are not affected); what a handle retains is its
+// arena, at most its budget (large_budget at first use), plus what the first
+// search allocated stream-ordered until the pool trims it at a
+// synchronisation.  At most budget bytes at a time: a nested launch sequence
+// (the list path's dense rows) gets what its caller's scratch leaves.
+struct Scratch {
+  hipStream_t st;
+  std::vector<void*> ptrs;
+  LargeArena* ar;
+  size_t start, total = 0;
+  explicit Scratch(hipStream_t s, LargeArena* a = nullptr)
+      : st(s), ar(a), start(a ? a->used : 0) {}
+  template <class T>
+  hipError_t get(T** p, int64_t n) {
+    *p = nullptr;
+    const size_t size = (sizeof(T) * (size_t)std::max<int64_t>(n, 1) + 255) & ~(size_t)255;
+    total += size;
+    if (ar && ar->base && ar->used + size <= ar->bytes) {
+      *p = reinterpret_cast<T*>(ar->base + ar->used);
+      ar->used += size;
+      return hipSuccess;
+    }
+    const hipError_t e = hipMallocAsync((void**)p, size, st);
+    if (e == hipSuccess) ptrs.push_back((void*)*p);
+    return e;
+  }
+  ~Scratch() {
+    if (ar) {
+      ar->need = std::max(ar->need, start + total);
+      ar->used = start;
+    }
+    for (void* p : ptrs) hipFreeAsync(p, st);
+  }
 };
 
 struct Workspace {
@@ -375,6 +423,56 @@ hipError_t launch_search_large_lists(const DevIndex& ix, const int32_t* d_querie
 hipError_t launch_merge_large(const int32_t* d_docs, const float* d_scores, int64_t W, int64_t Q,
                               int k, int64_t rank_stride, int32_t* d_out_docs,
                               float* d_out_scores, hipStream_t stream);
+
+// Filtered search (bm25_search_filtered).  Masks are [M][W] u32, W =
+// ceil(n_docs / 32), bit d & 31 of word d >> 5 = handle-local document d;
+// d_query_mask [Q] picks each query's mask (-1: no filter; null: mask 0 for
+// every query).  No kernel reads a mask word at index >= W, and bits at or
+// past n_docs never count.
+//
+// The tile passes (bm25mi_kernels.hip): the allowed documents of every (mask,
+// tile) into d_census[M][ntiles] and of every mask into d_total[M] (zeroed by
+// the caller); pass A: the best kTileM allowed keys of every (query, tile)
+// into d_cand[Q][ntiles][kTileM] (handle-local ids), no posting read where the
+// census is 0 (*d_skipped += those pairs); pass B: the pairs whose best key
+// is >= d_theta[q] scored again (*d_rescored += them), their allowed keys >=
+// theta appended to d_list[q][C] (d_list_cnt[q] counts past C: overflow).
+hipError_t launch_filter_census(const DevIndex& ix, const uint32_t* d_masks, int64_t M,
+                                int32_t* d_census, uint32_t* d_total, hipStream_t stream);
+hipError_t launch_filter_pass_a(const DevIndex& ix, const int32_t* d_queries, int64_t Q, int64_t T,
+                                const uint32_t* d_masks, const int32_t* d_query_mask,
+                                const int32_t* d_census, uint64_t* d_cand, int32_t* d_skipped,
+                                hipStream_t stream);
+hipError_t launch_filter_pass_b(const DevIndex& ix, const int32_t* d_queries, int64_t Q, int64_t T,
+                                const uint32_t* d_masks, const int32_t* d_query_mask,
+                                const uint64_t* d_cand, const uint64_t* d_theta, uint64_t* d_list,
+                                int32_t* d_list_cnt, int32_t C, int32_t* d_rescored,
+                                hipStream_t stream);
+// The dense path (bm25mi_large.hip), exact for every k, index and mask: per
+// chunk of queries the dense scores, the radix selection with the mask
+// applied where keys are formed and k_q = min(k, allowed documents of the
+// query's mask) (d_total, as launch_filter_census wrote it), the row sort and
+// the padded write.  d_ids (or null) names the nq rows of the batch to serve
+// (a device array): their queries are gathered and their results scattered
+// into d_docs / d_scores [Q][k]; otherwise nq = Q rows in order.
+hipError_t launch_search_filtered_dense(const DevIndex& ix, const int32_t* d_queries, int64_t T,
+                                        int k, const uint32_t* d_masks,
+                                        const int32_t* d_query_mask, const uint32_t* d_total,
+                                        const int32_t* d_ids, int64_t nq, int32_t* d_docs,
+                                        float* d_scores, hipStream_t stream, LargeArena* arena);
+// The whole filtered search (bm25mi_filter.hip): the census, then the tile
+// passes (k <= kMaxK and the filter_tiles option), theta, the lists' sort and
+// padded write, and the dense path for the queries whose list overflowed —
+// their number is read with the one host synchronisation of the call — or
+// the dense path for every query.  ws: the handle's workspace sized for (Q, T,
+// min(k, kMaxK)); counters [2] / [5] / [3] = queries handed to the dense path
+// by the tile passes / pairs pass A skipped / pairs pass B re-scored.
+// *n_dense: queries the dense path served.
+hipError_t launch_search_filtered(const DevIndex& ix, const int32_t* d_queries, int64_t Q,
+                                  int64_t T, int k, const uint32_t* d_masks, int64_t M,
+                                  const int32_t* d_query_mask, const Workspace& ws,
+                                  int32_t* d_docs, float* d_scores, int64_t* n_dense,
+                                  hipStream_t stream);
 
 // Largest token id of [n] device ids (0 if none is positive) into *d_out.
 hipError_t launch_max_token(const int32_t* d_queries, int64_t n, int32_t* d_out,

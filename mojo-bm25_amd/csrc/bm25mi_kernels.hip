@@ -4136,6 +4136,251 @@ hipError_t launch_merge_lists(const int32_t* d_docs, const float* d_scores, int6
   return hipGetLastError();
 }
 
+// ===========================================================================
+// Filtered search (bm25_search_filtered; orchestration in bm25mi_filter.hip,
+// DESIGN.md §4): the passes that need the tile accumulator.  Replaces no
+// reference call: BM25v.search has no filter (bm25_native.py:76-158).
+//
+// A mask row is W = ceil(n_docs / 32) u32 words, bit d & 31 of word d >> 5 =
+// handle-local document d; a tile of 2^S documents is 2^S / 32 whole words of
+// it (the last tile usually fewer: no word at index >= W is read, and bits at
+// or past n_docs never count).  One wave per (query, tile), the accumulator
+// in its own LDS slice as score_wave_kernel's, so every document's adds keep
+// the query-term order (add_item).
+// ===========================================================================
+
+// Allowed documents of every (mask, tile) and of every mask (total: zeroed by
+// the caller).  One wave per (mask, tile).
+__global__ __launch_bounds__(256) void filter_census_kernel(const uint32_t* __restrict__ masks,
+                                                            int64_t M, int64_t W, int64_t n_docs,
+                                                            int64_t ntiles, int S,
+                                                            int32_t* __restrict__ census,
+                                                            uint32_t* __restrict__ total) {
+  const int64_t tw = (int64_t)1 << (S - 5);  // words per tile
+  const int lane = lane_id();
+  const int64_t nitems = M * ntiles;
+  for (int64_t it = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); it < nitems;
+       it += (int64_t)gridDim.x * 4) {
+    const int64_t m = it / ntiles, tile = it - m * ntiles;
+    uint32_t c = 0;
+    for (int64_t j = lane; j < tw; j += 64) {
+      const int64_t w = tile * tw + j;
+      if (w >= W) continue;
+      uint32_t bits = masks[m * W + w];
+      const int64_t left = n_docs - 32 * w;  // (>= 1: w < W)
+      if (left < 32) bits &= (1u << left) - 1u;
+      c += (uint32_t)__popc(bits);
+    }
+    c = wave_sum_u32(c);
+    if (lane == 0) {
+      census[it] = (int32_t)c;
+      if (c) atomicAdd(total + m, c);
+    }
+  }
+}
+
+// Bit e of the result: this lane's entry e (tile-local doc entry_doc(e, lane))
+// is a candidate — allowed by the mask row (null: no filter) and below n_docs.
+// A lane's 2^S / 64 entries are runs of 4 consecutive documents, one run per
+// 256 documents: run j is a nibble of the tile's word 8 j + lane / 8.
+template <int S>
+__device__ __forceinline__ uint64_t lane_allow(const uint32_t* __restrict__ mrow, int64_t W,
+                                               int64_t tile, int64_t n_docs) {
+  constexpr int R = (1 << S) / 256;  // runs per lane
+  static_assert(R <= 16, "a lane's entries fit 64 bits");
+  const uint32_t lane = lane_id();
+  const int lim = (int)min<int64_t>(1 << S, n_docs - (tile << S));
+  uint64_t allow = 0;
+#pragma unroll
+  for (int j = 0; j < R; ++j) {
+    uint32_t nib = 0xFu;
+    if (mrow) {
+      const int64_t w = tile * ((1 << S) / 32) + 8 * j + (lane >> 3);
+      nib = w < W ? (mrow[w] >> (4u * (lane & 7u))) & 0xFu : 0u;
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      if ((int)entry_doc(4 * j + c, lane) >= lim) nib &= ~(1u << c);
+    allow |= (uint64_t)nib << (4 * j);
+  }
+  return allow;
+}
+
+struct FilterArgs {
+  const uint32_t* masks;      // [M][W]
+  const int32_t* query_mask;  // [Q] (null: mask 0 for every query); -1: no filter
+  const int32_t* census;      // [M][ntiles]
+  int64_t W;
+};
+
+__device__ __forceinline__ int32_t filter_mask_of(const FilterArgs& f, int64_t q) {
+  return f.query_mask ? f.query_mask[q] : 0;
+}
+
+// Pass A: the best kTileM allowed keys of every (query, tile), best first,
+// into cand[q][tile][kTileM] (handle-local doc ids; key 0: none).  A tile
+// whose census is 0 reads no posting.  Disallowed entries get the score bits
+// 0xFFFFFFFF, whose key is 0 (select_top's empty slot).
+template <int S>
+__global__ __launch_bounds__(64 * kWaves) void filter_pass_a_kernel(
+    IndexArgs a, const int32_t* __restrict__ queries, int32_t T, int64_t nq, FilterArgs f,
+    uint64_t* __restrict__ cand, int32_t* __restrict__ skipped) {
+  constexpr int D = 1 << S;
+  __shared__ __attribute__((aligned(16))) float acc_all[kWaves * D];
+  const int wave = uniform((int)(threadIdx.x >> 6));
+  float* acc = acc_all + wave * D;
+  // XCD x (blockIdx % 8) takes the tiles x, x + 8, ...: a tile's posting
+  // segments stay in one XCD's L2 (as score_wave_kernel's per-XCD ranges),
+  // and a contiguous range of allowed documents is spread over all of them
+  const int64_t xcd = blockIdx.x & 7;
+  const int64_t hi = ((a.ntiles - xcd + 7) >> 3) * nq;  // this XCD's items
+  const int64_t stride = (int64_t)(gridDim.x >> 3) * kWaves;
+  int64_t it = (int64_t)(blockIdx.x >> 3) * kWaves + wave;
+  if (it >= hi) return;  // wave-uniform; no barriers in this kernel
+  zero_acc<S>(acc);
+  int32_t nskip = 0;
+  for (; it < hi; it += stride) {
+    const int64_t tl = it / nq;  // tile-major: a tile's queries back to back
+    const int64_t q = it - tl * nq;
+    const int64_t tile = xcd + 8 * tl;
+    const int32_t m = filter_mask_of(f, q);
+    uint64_t* out = cand + (q * a.ntiles + tile) * kTileM;
+    if (m >= 0 && f.census[(int64_t)m * a.ntiles + tile] == 0) {  // wave-uniform
+      if (lane_id() < kTileM) out[lane_id()] = 0ull;
+      ++nskip;
+      continue;
+    }
+    const uint64_t allow = lane_allow<S>(m >= 0 ? f.masks + (int64_t)m * f.W : nullptr, f.W, tile,
+                                         a.n_docs);
+    add_item<S>(a, tile, queries + q * T, T, acc);
+    float fv[D / 64];
+    take_entries<S>(acc, fv);
+#pragma unroll
+    for (int e = 0; e < D / 64; ++e)
+      if (!((allow >> e) & 1u)) fv[e] = __uint_as_float(0xFFFFFFFFu);
+    select_top<S>(fv, tile, a.n_docs, kTileM, 0u, out);
+  }
+  if (nskip && lane_id() == 0) atomicAdd(skipped, nskip);
+}
+
+// Pass B: the (query, tile) pairs whose best pass-A key reaches theta[q] are
+// scored again and every allowed key >= theta is appended to the query's list
+// (one atomic per wave; a list past its capacity C only counts, as
+// emit_above's).  No other tile holds such a key.  A wave looks at 64 pairs
+// at a time (query-major: the 64 keys it tests are near each other).
+template <int S>
+__global__ __launch_bounds__(64 * kWaves) void filter_pass_b_kernel(
+    IndexArgs a, const int32_t* __restrict__ queries, int32_t T, int64_t nq, FilterArgs f,
+    const uint64_t* __restrict__ cand, const uint64_t* __restrict__ theta,
+    uint64_t* __restrict__ list, int32_t* __restrict__ list_cnt, int32_t C,
+    int32_t* __restrict__ rescored) {
+  constexpr int D = 1 << S;
+  constexpr int E = D / 64;
+  __shared__ __attribute__((aligned(16))) float acc_all[kWaves * D];
+  const int wave = uniform((int)(threadIdx.x >> 6));
+  float* acc = acc_all + wave * D;
+  const uint32_t lane = lane_id();
+  const int64_t nitems = a.ntiles * nq;
+  zero_acc<S>(acc);
+  int32_t nres = 0;
+  for (int64_t i0 = ((int64_t)blockIdx.x * kWaves + wave) * 64; i0 < nitems;
+       i0 += (int64_t)gridDim.x * kWaves * 64) {
+    const int64_t mine = i0 + lane;
+    bool hit = false;
+    if (mine < nitems) {
+      const uint64_t best = cand[mine * kTileM];  // (pair q * ntiles + tile)
+      hit = best != 0ull && best >= theta[mine / a.ntiles];
+    }
+    uint64_t hits = __ballot(hit);
+    while (hits != 0ull) {  // wave-uniform
+      const int l = __builtin_ctzll(hits);
+      hits &= hits - 1ull;
+      const int64_t it = i0 + l;
+      const int64_t q = it / a.ntiles, tile = it - q * a.ntiles;
+      const int32_t m = filter_mask_of(f, q);
+      const uint64_t th = theta[q];
+      const uint64_t allow = lane_allow<S>(m >= 0 ? f.masks + (int64_t)m * f.W : nullptr, f.W,
+                                           tile, a.n_docs);
+      add_item<S>(a, tile, queries + q * T, T, acc);
+      float fv[E];
+      take_entries<S>(acc, fv);
+      const int64_t base = tile << S;
+      int c = 0;
+#pragma unroll
+      for (int e = 0; e < E; ++e) {
+        const uint64_t key = make_key(fv[e], (uint32_t)(base + entry_doc(e, lane)));
+        c += (int)((allow >> e) & 1u) & (int)(key >= th);
+      }
+      ++nres;
+      if (__ballot(c > 0) == 0ull) continue;
+      const uint32_t incl = wave_incl_scan((uint32_t)c);
+      int pos = 0;
+      if (lane == 63) pos = atomicAdd(list_cnt + q, (int)incl);
+      pos = __shfl(pos, 63, 64) + (int)incl - c;
+      uint64_t* lq = list + q * C;
+#pragma unroll
+      for (int e = 0; e < E; ++e) {
+        const uint64_t key = make_key(fv[e], (uint32_t)(base + entry_doc(e, lane)));
+        if (((allow >> e) & 1u) && key >= th) {
+          if (pos < C) lq[pos] = key;
+          ++pos;
+        }
+      }
+    }
+  }
+  if (nres && lane == 0) atomicAdd(rescored, nres);
+}
+
+hipError_t launch_filter_census(const DevIndex& ix, const uint32_t* d_masks, int64_t M,
+                                int32_t* d_census, uint32_t* d_total, hipStream_t stream) {
+  if (M == 0 || ix.ntiles == 0) return hipSuccess;
+  const int64_t W = (ix.n_docs + 31) >> 5;
+  const unsigned grid = (unsigned)std::min<int64_t>((M * ix.ntiles + 3) / 4, 16384);
+  hipLaunchKernelGGL(filter_census_kernel, dim3(grid), dim3(256), 0, stream, d_masks, M, W,
+                     ix.n_docs, ix.ntiles, ix.tile_shift, d_census, d_total);
+  return hipGetLastError();
+}
+
+static FilterArgs filter_args(const DevIndex& ix, const uint32_t* d_masks,
+                              const int32_t* d_query_mask, const int32_t* d_census) {
+  return FilterArgs{d_masks, d_query_mask, d_census, (ix.n_docs + 31) >> 5};
+}
+
+hipError_t launch_filter_pass_a(const DevIndex& ix, const int32_t* d_queries, int64_t Q, int64_t T,
+                                const uint32_t* d_masks, const int32_t* d_query_mask,
+                                const int32_t* d_census, uint64_t* d_cand, int32_t* d_skipped,
+                                hipStream_t stream) {
+  if (Q == 0 || ix.ntiles == 0) return hipSuccess;
+  if (ix.tile_shift != BM25_TILE_SHIFT) return hipErrorInvalidValue;
+  constexpr int S = BM25_TILE_SHIFT;
+  // (a multiple of 8: one share of the workgroups per XCD)
+  const int64_t need = ((Q * ix.ntiles + 8 * kWaves - 1) / (8 * kWaves)) * 8;
+  const int grid =
+      (int)std::min<int64_t>(need, persistent_grid(filter_pass_a_kernel<S>, 64 * kWaves));
+  hipLaunchKernelGGL((filter_pass_a_kernel<S>), dim3((unsigned)grid), dim3(64 * kWaves), 0, stream,
+                     args_of(ix), d_queries, (int32_t)T, Q,
+                     filter_args(ix, d_masks, d_query_mask, d_census), d_cand, d_skipped);
+  return hipGetLastError();
+}
+
+hipError_t launch_filter_pass_b(const DevIndex& ix, const int32_t* d_queries, int64_t Q, int64_t T,
+                                const uint32_t* d_masks, const int32_t* d_query_mask,
+                                const uint64_t* d_cand, const uint64_t* d_theta, uint64_t* d_list,
+                                int32_t* d_list_cnt, int32_t C, int32_t* d_rescored,
+                                hipStream_t stream) {
+  if (Q == 0 || ix.ntiles == 0) return hipSuccess;
+  if (ix.tile_shift != BM25_TILE_SHIFT) return hipErrorInvalidValue;
+  constexpr int S = BM25_TILE_SHIFT;
+  const int64_t need = (Q * ix.ntiles + 64 * kWaves - 1) / (64 * kWaves);
+  const int grid =
+      (int)std::min<int64_t>(need, persistent_grid(filter_pass_b_kernel<S>, 64 * kWaves));
+  hipLaunchKernelGGL((filter_pass_b_kernel<S>), dim3((unsigned)grid), dim3(64 * kWaves), 0, stream,
+                     args_of(ix), d_queries, (int32_t)T, Q,
+                     filter_args(ix, d_masks, d_query_mask, nullptr), d_cand, d_theta, d_list,
+                     d_list_cnt, C, d_rescored);
+  return hipGetLastError();
+}
+
 }  // namespace bm25mi
 
 #if BM25_TRACE

@@ -64,10 +64,34 @@ __device__ __forceinline__ uint32_t wave_scan(uint32_t x) {
   return x;
 }
 
+// The filtered search's mask of each row of a chunk (MASKED instantiations;
+// the others ignore it): masks [M][W] u32, bit d & 31 of word d >> 5 =
+// document d; qm[g] = the row's mask (-1: no filter; qm null: mask 0);
+// total[m] = the documents mask m allows.
+struct MaskArgs {
+  const uint32_t* masks = nullptr;
+  const int32_t* qm = nullptr;
+  const uint32_t* total = nullptr;
+  int64_t W = 0;
+};
+__device__ __forceinline__ const uint32_t* mask_row(const MaskArgs& ma, int64_t g) {
+  const int32_t m = ma.qm ? ma.qm[g] : 0;
+  return m < 0 ? nullptr : ma.masks + (int64_t)m * ma.W;
+}
+
+// MASKED: row g wants k_g = min(k, its mask's allowed documents) keys (none:
+// decided at once, with no key).
+template <bool MASKED>
 __global__ __launch_bounds__(64) void lk_init_kernel(SelState* __restrict__ st, int64_t G,
-                                                     uint32_t k, int32_t* __restrict__ cnt) {
+                                                     uint32_t k, int32_t* __restrict__ cnt,
+                                                     MaskArgs ma) {
   for (int64_t g = threadIdx.x; g < G; g += 64) {
-    st[g] = SelState{0ull, k, 0u};
+    uint32_t need = k;
+    if constexpr (MASKED) {
+      const int32_t m = ma.qm ? ma.qm[g] : 0;
+      if (m >= 0) need = min(k, ma.total[m]);
+    }
+    st[g] = SelState{0ull, need, need == 0u ? 1u : 0u};
     cnt[g] = 0;
   }
 }
@@ -76,10 +100,11 @@ __global__ __launch_bounds__(64) void lk_init_kernel(SelState* __restrict__ st, 
 // (shift + 8) equal its prefix.  Exact zero sums (untouched documents, most
 // of a row) share one digit while shift >= 32 (their doc bits lie below it):
 // they are counted in a register, not with same-address LDS atomics.
+template <bool MASKED>
 __global__ __launch_bounds__(256) void lk_hist_kernel(const float* __restrict__ scores,
                                                       int64_t stride, int64_t n_docs, int shift,
                                                       const SelState* __restrict__ st,
-                                                      uint32_t* __restrict__ hist) {
+                                                      uint32_t* __restrict__ hist, MaskArgs ma) {
   __shared__ uint32_t h[256];
   const int64_t g = blockIdx.y;
   const SelState s = st[g];
@@ -95,6 +120,8 @@ __global__ __launch_bounds__(256) void lk_hist_kernel(const float* __restrict__ 
   const uint32_t zdig = (uint32_t)(zkey >> shift) & 255u;
   const float4* row = reinterpret_cast<const float4*>(scores + g * stride);
   const int64_t n4 = (n_docs + 3) >> 2;
+  const uint32_t* mrow = nullptr;
+  if constexpr (MASKED) mrow = mask_row(ma, g);
   uint32_t zeros = 0;
   const uint32_t lane = threadIdx.x & 63u;
   // every lane of a wave runs the same rounds (the ballots below)
@@ -103,17 +130,21 @@ __global__ __launch_bounds__(256) void lk_hist_kernel(const float* __restrict__ 
   for (int64_t r = 0; r < rounds; ++r) {
     const int64_t i = r * step + (int64_t)blockIdx.x * 256 + threadIdx.x;
     float fe[4] = {0.f, 0.f, 0.f, 0.f};
+    uint32_t mbits = 0xFu;  // the four documents' mask bits (word (4 i) >> 5 < W: 4 i < n_docs)
     if (i < n4) {
       const float4 f = row[i];
       fe[0] = f.x;
       fe[1] = f.y;
       fe[2] = f.z;
       fe[3] = f.w;
+      if constexpr (MASKED)
+        if (mrow) mbits = mrow[i >> 3] >> (4u * (uint32_t)(i & 7));
     }
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       const int64_t d = 4 * i + c;
       bool pend = d < n_docs;
+      if constexpr (MASKED) pend = pend && ((mbits >> c) & 1u);
       if (pend && zfast && __float_as_uint(fe[c]) == 0u) {
         zeros += zmatch ? 1u : 0u;
         pend = false;
@@ -188,11 +219,13 @@ __global__ __launch_bounds__(64) void lk_pick_kernel(SelState* __restrict__ st,
 // the stage's capacity (a zero-fill row's keys crowd into its first docs) take
 // the global atomic directly.
 constexpr int kCompactStage = 2048;
+template <bool MASKED>
 __global__ __launch_bounds__(256) void lk_compact_kernel(const float* __restrict__ scores,
                                                          int64_t stride, int64_t n_docs,
                                                          const SelState* __restrict__ st,
                                                          int32_t* __restrict__ cnt,
-                                                         uint64_t* __restrict__ keys, int64_t kk) {
+                                                         uint64_t* __restrict__ keys, int64_t kk,
+                                                         MaskArgs ma) {
   __shared__ uint64_t stage[kCompactStage];
   __shared__ int32_t n_stage, base;
   const int64_t g = blockIdx.y;
@@ -202,23 +235,29 @@ __global__ __launch_bounds__(256) void lk_compact_kernel(const float* __restrict
   __syncthreads();
   const float4* row = reinterpret_cast<const float4*>(scores + g * stride);
   const int64_t n4 = (n_docs + 3) >> 2;
+  const uint32_t* mrow = nullptr;
+  if constexpr (MASKED) mrow = mask_row(ma, g);
   // every lane of a wave runs the same rounds (ballots below)
   const int64_t step = (int64_t)gridDim.x * 256;
   const int64_t rounds = (n4 + step - 1) / step;
   for (int64_t r = 0; r < rounds; ++r) {
     const int64_t i = r * step + (int64_t)blockIdx.x * 256 + threadIdx.x;
     float fe[4] = {0.f, 0.f, 0.f, 0.f};
+    uint32_t mbits = 0xFu;  // (as lk_hist_kernel)
     if (i < n4) {
       const float4 f = row[i];
       fe[0] = f.x;
       fe[1] = f.y;
       fe[2] = f.z;
       fe[3] = f.w;
+      if constexpr (MASKED)
+        if (mrow) mbits = mrow[i >> 3] >> (4u * (uint32_t)(i & 7));
     }
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       const int64_t d = 4 * i + c;
-      const uint64_t key = d < n_docs ? doc_key(fe[c], (uint32_t)d) : 0ull;
+      uint64_t key = d < n_docs ? doc_key(fe[c], (uint32_t)d) : 0ull;
+      if constexpr (MASKED) key = ((mbits >> c) & 1u) ? key : 0ull;
       const bool keep = key != 0ull && key >= kth;
       const uint64_t m = __ballot(keep);
       if (m == 0ull) continue;
@@ -405,47 +444,7 @@ int64_t large_budget() {
   return std::max<int64_t>(64ll << 20, std::min<int64_t>((int64_t)free_b / 4, 4ll << 30));
 }
 
-// Scratch of one launch sequence.  With a handle's arena (LargeArena) the
-// buffers come from it; what does not fit is allocated stream-ordered,
-// released on `st` after everything enqueued so far, and counted, so the host
-// grows the arena before the handle's next search: a large-k search then
-// allocates nothing (each stream-ordered allocation and free cost the host
-// ~0.1 ms: ~2 ms per search at c3, k = 10 000, before its first kernel).  The
-// device's default pool keeps its default release threshold (the process's
-// other users of the pool are not affected); what a handle retains is its
-// arena, at most its budget (large_budget at first use), plus what the first
-// search allocated stream-ordered until the pool trims it at a
-// synchronisation.  At most budget bytes at a time: a nested launch sequence
-// (the list path's dense rows) gets what its caller's scratch leaves.
-struct Scratch {
-  hipStream_t st;
-  std::vector<void*> ptrs;
-  LargeArena* ar;
-  size_t start, total = 0;
-  explicit Scratch(hipStream_t s, LargeArena* a = nullptr)
-      : st(s), ar(a), start(a ? a->used : 0) {}
-  template <class T>
-  hipError_t get(T** p, int64_t n) {
-    *p = nullptr;
-    const size_t size = (sizeof(T) * (size_t)std::max<int64_t>(n, 1) + 255) & ~(size_t)255;
-    total += size;
-    if (ar && ar->base && ar->used + size <= ar->bytes) {
-      *p = reinterpret_cast<T*>(ar->base + ar->used);
-      ar->used += size;
-      return hipSuccess;
-    }
-    const hipError_t e = hipMallocAsync((void**)p, size, st);
-    if (e == hipSuccess) ptrs.push_back((void*)*p);
-    return e;
-  }
-  ~Scratch() {
-    if (ar) {
-      ar->need = std::max(ar->need, start + total);
-      ar->used = start;
-    }
-    for (void* p : ptrs) hipFreeAsync(p, st);
-  }
-};
+// (Scratch, a launch sequence's scratch from the handle's arena: bm25mi_internal.h)
 
 // The byte budget of one large-k launch sequence: the arena's, fixed at its
 // first use (hipMemGetInfo costs the host too), else the device's free memory.
@@ -503,15 +502,16 @@ hipError_t launch_search_large(const DevIndex& ix, const int32_t* d_queries, int
   for (int64_t q0 = 0; q0 < Q; q0 += G) {
     const int64_t g = std::min<int64_t>(G, Q - q0);
     LK_TRY(launch_scores_batch(ix, d_queries + q0 * T, g, T, Np, scores, st));
-    hipLaunchKernelGGL(lk_init_kernel, dim3(1), dim3(64), 0, st, state, g, (uint32_t)kv, cnt);
+    hipLaunchKernelGGL(lk_init_kernel<false>, dim3(1), dim3(64), 0, st, state, g, (uint32_t)kv,
+                       cnt, MaskArgs{});
     const dim3 grid(grid_for(n4, 256 * 8, 1024), (unsigned)g);
     for (int shift = 56; shift >= 0; shift -= 8) {
-      hipLaunchKernelGGL(lk_hist_kernel, grid, dim3(256), 0, st, scores, Np, ix.n_docs, shift,
-                         state, hist);
+      hipLaunchKernelGGL(lk_hist_kernel<false>, grid, dim3(256), 0, st, scores, Np, ix.n_docs,
+                         shift, state, hist, MaskArgs{});
       hipLaunchKernelGGL(lk_pick_kernel, dim3((unsigned)g), dim3(64), 0, st, state, hist, shift);
     }
-    hipLaunchKernelGGL(lk_compact_kernel, grid, dim3(256), 0, st, scores, Np, ix.n_docs, state, cnt,
-                       keys, (int64_t)kv);
+    hipLaunchKernelGGL(lk_compact_kernel<false>, grid, dim3(256), 0, st, scores, Np, ix.n_docs,
+                       state, cnt, keys, (int64_t)kv, MaskArgs{});
     if (!lds_sort_write(keys, g, kv, k, ix.doc_offset, d_docs + q0 * k, d_scores + q0 * k, st)) {
       const uint64_t* sorted = nullptr;
       LK_TRY(sort_rows(keys, alt, g, kv, tmp, &sorted, st));
@@ -928,6 +928,95 @@ hipError_t launch_search_large_lists(const DevIndex& ix, const int32_t* d_querie
                      fs, d_ids, nf, (int64_t)k, d_docs, d_scores);
   // (ids lives on the host until the copy above has run)
   LK_TRY(hipStreamSynchronize(st));
+  return hipGetLastError();
+}
+
+// The filtered search's dense path: launch_search_large's sequence with the
+// mask applied where keys are formed and a per-row k_q; a row's unused key
+// slots stay 0 (cleared per chunk) and sort last, written as padding.
+hipError_t launch_search_filtered_dense(const DevIndex& ix, const int32_t* d_queries, int64_t T,
+                                        int k, const uint32_t* d_masks,
+                                        const int32_t* d_query_mask, const uint32_t* d_total,
+                                        const int32_t* d_ids, int64_t nq, int32_t* d_docs,
+                                        float* d_scores, hipStream_t st, LargeArena* arena) {
+  if (nq == 0 || k == 0) return hipSuccess;
+  if (k > ix.n_docs) return hipErrorInvalidValue;
+  ix.disp.kernels |= kKLarge;
+  const int64_t Np = ix.ntiles << ix.tile_shift;
+  Scratch sc(st, arena);
+  // a subset of the batch: its queries and mask ids gathered, its results
+  // scattered back
+  const int32_t* q = d_queries;
+  const int32_t* qm = d_query_mask;
+  int32_t* od = d_docs;
+  float* os = d_scores;
+  if (d_ids) {
+    int32_t *fq = nullptr, *fm = nullptr;
+    LK_TRY(sc.get(&fq, nq * std::max<int64_t>(T, 1)));
+    LK_TRY(sc.get(&od, nq * k));
+    LK_TRY(sc.get(&os, nq * k));
+    if (T > 0)
+      hipLaunchKernelGGL(gather_rows_kernel, dim3(grid_for(nq * T, 256, 4096)), dim3(256), 0, st,
+                         d_queries, d_ids, nq, T, fq);
+    q = fq;
+    if (d_query_mask) {
+      LK_TRY(sc.get(&fm, nq));
+      hipLaunchKernelGGL(gather_rows_kernel, dim3(grid_for(nq, 256, 4096)), dim3(256), 0, st,
+                         d_query_mask, d_ids, nq, (int64_t)1, fm);
+      qm = fm;
+    }
+  }
+  const int64_t per_q = Np * 4 + (int64_t)k * 16 + 256 * 4 + 64 + sort_bytes(1, k);
+  const int64_t budget =
+      std::max<int64_t>(budget_of(arena) - (int64_t)(arena ? arena->used : 0), 64ll << 20);
+  int64_t G = std::max<int64_t>(1, std::min<int64_t>(nq, budget / per_q));
+  G = std::min<int64_t>(G, 65535);
+  G = std::min<int64_t>(G, std::max<int64_t>(1, (int64_t)INT32_MAX / k - 1));
+  float* scores = nullptr;
+  uint32_t* hist = nullptr;
+  SelState* state = nullptr;
+  int32_t* cnt = nullptr;
+  uint64_t *keys = nullptr, *alt = nullptr;
+  char* tmp = nullptr;
+  LK_TRY(sc.get(&scores, G * Np));
+  LK_TRY(sc.get(&hist, G * 256));
+  LK_TRY(sc.get(&state, G));
+  LK_TRY(sc.get(&cnt, G));
+  LK_TRY(sc.get(&keys, G * k));
+  LK_TRY(sc.get(&alt, G * k));
+  LK_TRY(sc.get(&tmp, sort_bytes(G, k)));
+  LK_TRY(hipMemsetAsync(hist, 0, sizeof(uint32_t) * G * 256, st));
+  const int64_t n4 = (ix.n_docs + 3) >> 2;
+  MaskArgs ma;
+  ma.masks = d_masks;
+  ma.total = d_total;
+  ma.W = (ix.n_docs + 31) >> 5;
+  for (int64_t q0 = 0; q0 < nq; q0 += G) {
+    const int64_t g = std::min<int64_t>(G, nq - q0);
+    ma.qm = qm ? qm + q0 : nullptr;
+    LK_TRY(launch_scores_batch(ix, q + q0 * T, g, T, Np, scores, st));
+    LK_TRY(hipMemsetAsync(keys, 0, sizeof(uint64_t) * g * k, st));
+    hipLaunchKernelGGL(lk_init_kernel<true>, dim3(1), dim3(64), 0, st, state, g, (uint32_t)k, cnt,
+                       ma);
+    const dim3 grid(grid_for(n4, 256 * 8, 1024), (unsigned)g);
+    for (int shift = 56; shift >= 0; shift -= 8) {
+      hipLaunchKernelGGL(lk_hist_kernel<true>, grid, dim3(256), 0, st, scores, Np, ix.n_docs,
+                         shift, state, hist, ma);
+      hipLaunchKernelGGL(lk_pick_kernel, dim3((unsigned)g), dim3(64), 0, st, state, hist, shift);
+    }
+    hipLaunchKernelGGL(lk_compact_kernel<true>, grid, dim3(256), 0, st, scores, Np, ix.n_docs,
+                       state, cnt, keys, (int64_t)k, ma);
+    if (!lds_sort_write(keys, g, k, k, ix.doc_offset, od + q0 * k, os + q0 * k, st)) {
+      const uint64_t* sorted = nullptr;
+      LK_TRY(sort_rows(keys, alt, g, k, tmp, &sorted, st));
+      hipLaunchKernelGGL(lk_write_kernel, dim3(grid_for(g * k, 256, 4096)), dim3(256), 0, st,
+                         sorted, (int64_t)k, g, k, k, ix.doc_offset, od + q0 * k, os + q0 * k);
+    }
+    LK_TRY(hipGetLastError());
+  }
+  if (d_ids)
+    hipLaunchKernelGGL(scatter_rows_kernel, dim3(grid_for(nq * k, 256, 4096)), dim3(256), 0, st,
+                       od, os, d_ids, nq, (int64_t)k, d_docs, d_scores);
   return hipGetLastError();
 }
 
