@@ -296,6 +296,80 @@ int bm25_search_filtered_device(bm25_index* idx, const int32_t* d_queries, int64
 int bm25_search_filtered_stats(bm25_index* idx, int64_t* out, int32_t n);
 
 /*
+ * Boolean term filters: the allow-masks of "+rust -java" — must contain all
+ * of these terms, at least one of those, none of these — built on the device
+ * from the index's own postings, in exactly the layout
+ * bm25_search_filtered_device reads.
+ * Replaces no reference call: BM25v.search has no term filter
+ * (bm25_native.py:76-158).
+ *   has(t, d) is true when the CSC index stores a posting for (term t,
+ *   handle-local document d); a stored 0.0f or a negative value counts.
+ *   Mask row m, from three clause rows of token ids and an optional base mask:
+ *     allowed(m, d) =  d < n_docs
+ *                  and base(m, d)                              (absent base: true)
+ *                  and for every id t >= 0 in must[m]:      has(t, d)
+ *                  and (any[m] holds no id >= 0  or  some id t >= 0 in any[m] has(t, d))
+ *                  and no id t >= 0 in must_not[m]:         has(t, d)
+ *   must [M, A], any [M, B], must_not [M, N] int32, rows contiguous.  Negative
+ *              ids are padding; duplicate ids are harmless; a width of 0 (the
+ *              pointer may then be NULL) is an empty clause.  A term in both
+ *              must and must_not gives an empty mask; all three clauses empty
+ *              give base, or every document when there is no base.
+ *   base       [Mb, W] uint32, Mb = 0 (NULL: no base), 1 (applied to every
+ *              row) or M; the bit layout of bm25_search_filtered: document d
+ *              at bit d & 31 of word d >> 5, handle-local documents.
+ *   out_masks  [M, W] uint32, W = ceil(n_docs / 32).  Every word of every row
+ *              is written (the caller need not zero the buffer); the bits at
+ *              or past n_docs of the last word are written 0 even where base
+ *              has them set; no word at index >= W of a row is read or
+ *              written, nothing past M * W words is touched.
+ * Memory: the masks take M * W * 4 bytes — 1.25 MB per mask at 10M documents;
+ * built here they never cross the host link.
+ * Doc shards: bits are by the handle's own documents, so a shard builds its
+ * slice of the collection's mask from its own postings, and the shards'
+ * filtered lists still merge through bm25_merge_topk_device unchanged.
+ *   bm25_term_masks: host buffers, validated, synchronous; staged through
+ *     device buffers of the call's own.  M == 0 returns BM25_OK without device
+ *     work.  Errors: EINVAL for a NULL index, negative shapes, NULL pointers
+ *     with non-empty shapes, Mb not in {0, 1, M}, and an id >= n_terms (the
+ *     message matches bm25_native.py:118-121, as bm25_search).
+ *   bm25_term_masks_device: device buffers, enqueued on `stream`; validates no
+ *     id and never synchronises (shapes and NULL pointers are checked as
+ *     above).  Here an id >= n_terms is a term that no document has: in must
+ *     it empties the row, in any it makes the clause active and matches
+ *     nothing, in must_not it removes nothing — on purpose NOT the "padding"
+ *     of bm25_search_device, where dropping an unknown term only loses its
+ *     score; dropping it from must would let every document through.  The call
+ *     reads the immutable index arrays only — not the search workspace — and
+ *     is not ordered against the handle's searches: it may run on its own
+ *     stream while a search of the same handle is in flight on another (as
+ *     bm25_score_docs_device).  No global atomics, no scratch: the result
+ *     does not depend on scheduling.
+ *   bm25_search_boolean: bm25_search_filtered under the masks of Q clause
+ *     rows (M = Q, Mb in {0, 1, Q}), host buffers, validated, synchronous: row
+ *     q is bit for bit the row bm25_search_filtered returns for query q under
+ *     the mask of clause row q, padding included (doc -1 / score bits
+ *     0xFFFFFFFF where fewer than k documents qualify).  The masks are built
+ *     on the device and never move to the host.  The batch is served in
+ *     chunks of queries so that the call's mask buffer — its own, allocated
+ *     and released inside the call — stays bounded: option "bool_chunk"
+ *     queries per chunk, automatically at most 1 GiB of mask words and at
+ *     least one query.  Errors: those of bm25_search_filtered and of
+ *     bm25_term_masks.
+ */
+int bm25_term_masks(bm25_index* idx, const int32_t* must, int64_t A, const int32_t* any, int64_t B,
+                    const int32_t* must_not, int64_t N, int64_t M, const uint32_t* base,
+                    int64_t Mb, uint32_t* out_masks);
+int bm25_term_masks_device(bm25_index* idx, const int32_t* d_must, int64_t A, const int32_t* d_any,
+                           int64_t B, const int32_t* d_must_not, int64_t N, int64_t M,
+                           const uint32_t* d_base, int64_t Mb, uint32_t* d_out_masks,
+                           void* stream);
+int bm25_search_boolean(bm25_index* idx, const int32_t* queries, int64_t Q, int64_t T, int32_t k,
+                        const int32_t* must, int64_t A, const int32_t* any, int64_t B,
+                        const int32_t* must_not, int64_t N, const uint32_t* base, int64_t Mb,
+                        int32_t* out_docs, float* out_scores);
+
+/*
  * bm25.BM25's float64 path (the dense model's API keeps the reference's
  * precision).  bm25_index_set_values_f64 keeps a float64 copy of the index's
  * values beside it (the same CSC order; bm25_build_scores method 1 returns
@@ -498,7 +572,7 @@ int bm25_search_counters(bm25_index* idx, int64_t* out, int32_t n);
  * environment (BM25_FLAT, BM25_FLAT_BW, BM25_ITEMS_PER_WAVE, BM25_SAMPLE_P,
  * BM25_LIST_CAP, BM25_CLAIM_CH, BM25_CLAIM_M, BM25_TILE_BOUND, BM25_THETA_BOUND,
  * BM25_GRID_PCT, BM25_LARGE_LISTS, BM25_COUNT_SKIPS, BM25_REST_SPLIT,
- * BM25_BOUND_POOL, BM25_FILTER_TILES) at
+ * BM25_BOUND_POOL, BM25_FILTER_TILES, BM25_BOOL_CHUNK) at
  * bm25_index_create; these
  * calls change or read them afterwards, effective from the next search.
  * Results never depend on them (every setting is bit-exact); they choose
@@ -552,7 +626,10 @@ int bm25_search_counters(bm25_index* idx, int64_t* out, int32_t n);
  *                    bounds
  *   "filter_tiles"   1 (default): a filtered search of k <= 4096 takes the tile
  *                    passes; 0: dense score rows for every query
- *   "grid_pct"       percent of the device's resident workgroup slots the
+ *   "bool_chunk"     bm25_search_boolean: queries per chunk of device-built
+ *                    masks (env BM25_BOOL_CHUNK); 0 (default) = automatic: at
+ *                    most 1 GiB of mask words per chunk, at least one query
+ *   "grid_pct"      percent of the device's resident workgroup slots the
  *                    persistent score kernels launch (1..100, default 100):
  *                    below 100 leaves slots for kernels of another stream
  *                    (a concurrent search on a fork, the collectives)

@@ -157,6 +157,47 @@ class BM25v:
         return self._gpu.search_filtered(queries, top_k, allow,
                                          np.arange(queries.shape[0], dtype=np.int32))
 
+    def search_boolean(self, queries, top_k: int, must=None, any=None, must_not=None,
+                       base=None) -> Tuple[np.ndarray, np.ndarray]:
+        """search under boolean term filters (not in the reference, whose
+        search has no term filter): query q ranks only the documents that hold
+        every term of ``must[q]``, at least one of ``any[q]`` (when it names
+        one) and none of ``must_not[q]`` — "+a +b -c" — and that ``base``
+        allows (a bool [n_docs] mask for every query or [Q, n_docs], or packed
+        rows of bm25mi.pack_mask).  Clauses are int32 [Q, width] arrays or
+        ragged lists of lists of token ids (negative = padding), or None.
+        Returns search_filtered's tuple; the masks are built on the GPU."""
+        if len(queries) == 0:
+            return np.zeros((0, 0), dtype=self.dtype), np.zeros((0, 0), dtype=self.dtype)
+        if (not isinstance(queries, np.ndarray) or queries.ndim != 2
+                or not isinstance(queries[0][0], TokId)):
+            raise ValueError("The queries must be a list of list of query token IDs.")
+        from bm25mi.index import pad_clause
+        Q = queries.shape[0]
+        clauses = []
+        for name, c in (("must", must), ("any", any), ("must_not", must_not)):
+            c = None if c is None else pad_clause(c)
+            if c is not None and c.shape[0] != Q:
+                raise ValueError(f"{name} must have one row per query ({Q}), got {c.shape[0]}.")
+            clauses.append(c)
+        if base is not None:
+            base = np.asarray(base)
+            if base.ndim not in (1, 2) or (base.ndim == 2 and base.shape[0] not in (1, Q)):
+                raise ValueError("base must be a [n_docs] mask or a [Q, n_docs] array with one "
+                                 "row per query.")
+        if top_k < 0:
+            raise ValueError("negative dimensions are not allowed")
+        max_token_id = max([int(queries.max(initial=0))]
+                           + [int(c.max(initial=0)) for c in clauses if c is not None])
+        n_terms = self._gpu.n_terms if self._gpu is not None else len(self.doc_toks.indptr) - 1
+        if max_token_id >= n_terms:
+            raise ValueError(
+                f"The maximum token ID in the query ({max_token_id}) is higher than the number "
+                "of tokens in the index.")
+        if self._gpu is None:
+            raise ValueError("BM25v index not built. Call index() first.")
+        return self._gpu.search_boolean(queries, top_k, clauses[0], clauses[1], clauses[2], base)
+
     def _compute_relevance_from_scores(self, queries, top_k: int, dtype=np.float32):
         """bm25_native.py:129-158 on the GPU: per query, negative ids dropped,
         postings gathered, fp32 sums in query order, top-k."""

@@ -64,6 +64,11 @@ _SIGS = {
     "bm25_search_filtered_device": ([_P, _P, _I64, _I64, _I32, _P, _I64, _P, _P, _P, _P],
                                     ctypes.c_int),
     "bm25_search_filtered_stats": ([_P, _PI64, _I32], ctypes.c_int),
+    "bm25_term_masks": ([_P, _P, _I64, _P, _I64, _P, _I64, _I64, _P, _I64, _P], ctypes.c_int),
+    "bm25_term_masks_device": ([_P, _P, _I64, _P, _I64, _P, _I64, _I64, _P, _I64, _P, _P],
+                               ctypes.c_int),
+    "bm25_search_boolean": ([_P, _P, _I64, _I64, _I32, _P, _I64, _P, _I64, _P, _I64, _P, _I64,
+                             _P, _P], ctypes.c_int),
     "bm25_index_set_values_f64": ([_P, _P], ctypes.c_int),
     "bm25_scores_dense_f64": ([_P, _P, _I64, _P], ctypes.c_int),
     "bm25_topn_f64": ([_P, _P, _I64, _I64, _P, _P], ctypes.c_int),

@@ -37,6 +37,29 @@ def pack_mask(allow) -> np.ndarray:
     return np.ascontiguousarray(packed).view("<u4").astype(np.uint32, copy=False).reshape(M, W)
 
 
+def pad_clause(rows) -> np.ndarray:
+    """Clause rows for the boolean term filters: an int [M, width] array, or
+    a ragged list of lists of token ids -> int32 [M, width], short rows padded
+    with -1 (padding)."""
+    if not isinstance(rows, np.ndarray):
+        rows = list(rows)
+        if any(not isinstance(r, np.ndarray) and np.ndim(r) == 0 for r in rows):
+            raise ValueError("a clause must be a 2-D [M, width] array or a list of lists of "
+                             "token ids")
+        if len({len(r) for r in rows}) > 1 or not rows:
+            width = max((len(r) for r in rows), default=0)
+            a = np.full((len(rows), width), -1, np.int32)
+            for i, r in enumerate(rows):
+                a[i, :len(r)] = np.asarray(r, np.int32)
+            return a
+        rows = np.asarray(rows)
+        if rows.size == 0:
+            rows = rows.reshape(len(rows), 0)
+    if rows.ndim != 2 or (rows.size and rows.dtype.kind not in "iu"):
+        raise ValueError("a clause must be a 2-D [M, width] array or a list of lists of token ids")
+    return np.ascontiguousarray(rows, dtype=np.int32)
+
+
 class GpuIndex:
     """A doc x term CSC score matrix resident in HBM.
 
@@ -390,6 +413,108 @@ class GpuIndex:
         check(lib.bm25_search_filtered_stats(self._h, v, 3))
         return int(v[0]), int(v[1]), int(v[2])
 
+    # -------------------------------------------------- boolean term filters
+    def _clauses_arg(self, must, any, must_not, base, rows=None):
+        """The clause rows of term_masks / search_boolean: each of must, any,
+        must_not an int32 [M, width] array, a ragged list of lists of token
+        ids (padded with -1 here) or None (an empty clause); base as
+        search_filtered's masks, 1 or M rows, or None.  ``rows``: the row
+        count the caller fixes (the queries of search_boolean).  Returns
+        (must, any, must_not, M, base, Mb); shape errors are raised here,
+        before any C call."""
+        out, M = [], rows
+        for name, c in (("must", must), ("any", any), ("must_not", must_not)):
+            if c is None:
+                out.append(None)
+                continue
+            a = pad_clause(c)
+            if M is None:
+                M = a.shape[0]
+            elif a.shape[0] != M:
+                raise ValueError(f"{name} has {a.shape[0]} rows, expected {M} (one per "
+                                 f"{'query' if rows is not None else 'mask'})")
+            out.append(a)
+        b, Mb = None, 0
+        if base is not None:
+            b = self._masks_arg(base)
+            Mb = b.shape[0]
+            if M is None:
+                M = Mb
+            elif Mb not in (1, M):
+                raise ValueError(f"base has {Mb} rows, expected 1 or {M}")
+        if M is None:
+            raise ValueError("no clause and no base given: the number of masks is unknown")
+        out = [np.zeros((M, 0), np.int32) if a is None else a for a in out]
+        return out[0], out[1], out[2], M, b, Mb
+
+    def term_masks(self, must=None, any=None, must_not=None, base=None) -> np.ndarray:
+        """Allow-masks of boolean term filters (bm25_term_masks, host arrays)
+        -> packed uint32 [M, W], W = ceil(n_docs / 32), the masks
+        search_filtered takes: row m allows the documents of this handle that
+        hold every term of must[m], at least one of any[m] (when it names
+        one), none of must_not[m], and that base allows.  Clauses: int32
+        [M, width] arrays or ragged lists of lists (negative ids = padding);
+        base: bool [n_docs] / [M, n_docs] or packed uint32 rows, 1 or M."""
+        mu, an, mn, M, b, Mb = self._clauses_arg(must, any, must_not, base)
+        out = np.zeros((M, (self.n_docs + 31) // 32), np.uint32)
+        check(lib.bm25_term_masks(self._h, _ptr(mu), mu.shape[1], _ptr(an), an.shape[1], _ptr(mn),
+                                  mn.shape[1], M, _ptr(b) if Mb else None, Mb, _ptr(out)))
+        return out
+
+    def term_masks_device(self, d_must, d_any, d_must_not, d_base, d_out, stream=None) -> None:
+        """Device-resident term_masks (bm25_term_masks_device): torch int32
+        [M, width] clause tensors (or None: an empty clause), packed base
+        masks [1 or M, W] (or None) in, packed masks d_out [M, W] (32-bit
+        words) out, enqueued on ``stream`` with no host synchronisation and no
+        validation of ids — an id >= n_terms is a term that no document has.
+        Reads the index arrays only, so it may overlap a search of the same
+        handle on another stream."""
+        W = (self.n_docs + 31) // 32
+        if d_out.dim() != 2 or d_out.shape[1] != W or d_out.element_size() != 4:
+            raise ValueError(f"d_out must be a packed [M, {W}] tensor of 32-bit words")
+        M = d_out.shape[0]
+        args = []
+        for name, c in (("d_must", d_must), ("d_any", d_any), ("d_must_not", d_must_not)):
+            if c is None:
+                args += [None, 0]
+                continue
+            if c.dim() != 2 or c.element_size() != 4:
+                raise ValueError(f"{name} must be a 2-D [M, width] int32 tensor")
+            if c.shape[0] != M:
+                raise ValueError(f"{name} has {c.shape[0]} rows, d_out has {M}")
+            args += [ctypes.c_void_p(c.data_ptr()) if c.shape[1] else None, c.shape[1]]
+        Mb = 0
+        if d_base is not None:
+            if d_base.dim() != 2 or d_base.shape[1] != W or d_base.element_size() != 4:
+                raise ValueError(f"d_base must be a packed [1 or M, {W}] tensor of 32-bit words")
+            Mb = d_base.shape[0]
+            if Mb not in (1, M):
+                raise ValueError(f"d_base has {Mb} rows, expected 1 or {M}")
+        s = getattr(stream, "cuda_stream", stream) or 0
+        check(lib.bm25_term_masks_device(
+            self._h, *args, M, ctypes.c_void_p(d_base.data_ptr()) if Mb else None, Mb,
+            ctypes.c_void_p(d_out.data_ptr()), ctypes.c_void_p(s)))
+
+    def search_boolean(self, queries: np.ndarray, k: int, must=None, any=None, must_not=None,
+                       base=None) -> Tuple[np.ndarray, np.ndarray]:
+        """Top-k of every query among the documents its clause row lets
+        through (bm25_search_boolean, host arrays): search_filtered under
+        term_masks(must, any, must_not, base) with one mask per query, the
+        masks built on the device and never moved to the host.  Clauses and
+        base as term_masks, with one row per query (base: 1 row or Q)."""
+        q = np.ascontiguousarray(queries, dtype=np.int32)
+        if q.ndim != 2:
+            raise ValueError("queries must be a 2-D [Q, T] int32 array")
+        Q, T = q.shape
+        mu, an, mn, _, b, Mb = self._clauses_arg(must, any, must_not, base, rows=Q)
+        k = int(k)
+        docs = np.zeros((Q, max(k, 0)), np.int32)
+        scores = np.zeros((Q, max(k, 0)), np.float32)
+        check(lib.bm25_search_boolean(self._h, _ptr(q), Q, T, k, _ptr(mu), mu.shape[1], _ptr(an),
+                                      an.shape[1], _ptr(mn), mn.shape[1],
+                                      _ptr(b) if Mb else None, Mb, _ptr(docs), _ptr(scores)))
+        return docs, scores
+
     # ------------------------------------------- bm25.BM25's float64 path
     def set_values_f64(self, data64) -> None:
         """Keep a float64 copy of the values (same CSC order) on the device
@@ -434,7 +559,7 @@ class GpuIndex:
     def set_option(self, name: str, value: int) -> None:
         """A search option of this handle (bm25_index_set_option: flat,
         flat_bw, items_per_wave, sample_p, list_cap, claim_ch, claim_m,
-        tile_bound, theta_bound, filter_tiles, ...).  In a multi-rank search every rank must
+        tile_bound, theta_bound, filter_tiles, bool_chunk, ...).  In a multi-rank search every rank must
         change an option together (like a collective): the next
         ``bm25mi.dist.sharded_search`` re-checks the sample width they agree on."""
         check(lib.bm25_index_set_option(self._h, name.encode(), int(value)))

@@ -154,6 +154,7 @@ SearchOpts env_opts() {
   o.rest_split = env_int("BM25_REST_SPLIT", o.rest_split) != 0;
   o.bound_pool = env_int("BM25_BOUND_POOL", o.bound_pool) != 0;
   o.filter_tiles = env_int("BM25_FILTER_TILES", o.filter_tiles) != 0;
+  o.bool_chunk = std::max(0, env_int("BM25_BOOL_CHUNK", o.bool_chunk));
   return o;
 }
 
@@ -201,6 +202,9 @@ int set_opt(SearchOpts& o, const char* name, int64_t v) {
   } else if (n == "filter_tiles") {
     if (v != 0 && v != 1) return fail(BM25_EINVAL, "filter_tiles must be 0 or 1");
     o.filter_tiles = (int)v;
+  } else if (n == "bool_chunk") {
+    if (v < 0 || v > (1 << 30)) return fail(BM25_EINVAL, "bool_chunk must be in 0..2^30");
+    o.bool_chunk = (int)v;
   } else if (n == "count_skips") {
     if (v != 0 && v != 1) return fail(BM25_EINVAL, "count_skips must be 0 or 1");
     o.count_skips = (int)v;
@@ -231,6 +235,7 @@ int get_opt(const SearchOpts& o, const char* name, int64_t* v) {
   else if (n == "rest_split") *v = o.rest_split;
   else if (n == "bound_pool") *v = o.bound_pool;
   else if (n == "filter_tiles") *v = o.filter_tiles;
+  else if (n == "bool_chunk") *v = o.bool_chunk;
   else return fail(BM25_EINVAL, "unknown option '%s'", name);
   return BM25_OK;
 }
@@ -980,6 +985,189 @@ int bm25_search_filtered_stats(bm25_index* h, int64_t* out, int32_t n) {
   const bool tiles = (h->ix.disp.kernels & kKFiltered) != 0;
   const int64_t v[3] = {h->filtered_dense, tiles ? cnt[5] : 0, tiles ? cnt[3] : 0};
   for (int i = 0; i < n; ++i) out[i] = v[i];
+  return BM25_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// The clause arguments of the term-mask calls: shapes and pointers.
+int check_clauses(const void* must, int64_t A, const void* any, int64_t B, const void* must_not,
+                  int64_t N, int64_t M, const void* base, int64_t Mb) {
+  if (A < 0 || B < 0 || N < 0 || M < 0 || Mb < 0)
+    return fail(BM25_EINVAL, "negative clause or mask shape");
+  if (Mb != 0 && Mb != 1 && Mb != M)
+    return fail(BM25_EINVAL, "base masks: Mb = %lld must be 0, 1 or M = %lld", (long long)Mb,
+                (long long)M);
+  if (M == 0) return BM25_OK;
+  if (A > 0 && !must) return fail(BM25_EINVAL, "NULL must");
+  if (B > 0 && !any) return fail(BM25_EINVAL, "NULL any");
+  if (N > 0 && !must_not) return fail(BM25_EINVAL, "NULL must_not");
+  if (Mb > 0 && !base) return fail(BM25_EINVAL, "NULL base");
+  return BM25_OK;
+}
+
+// bm25_native.py:116-121 over the clause ids: max(initial = mx) >= n_terms -> ValueError
+int check_clause_ids(const bm25_index* h, int64_t mx, const int32_t* must, int64_t A,
+                     const int32_t* any, int64_t B, const int32_t* must_not, int64_t N, int64_t M) {
+  for (int64_t i = 0; i < M * A; ++i) mx = std::max<int64_t>(mx, must[i]);
+  for (int64_t i = 0; i < M * B; ++i) mx = std::max<int64_t>(mx, any[i]);
+  for (int64_t i = 0; i < M * N; ++i) mx = std::max<int64_t>(mx, must_not[i]);
+  if (mx >= h->ix.n_terms)
+    return fail(BM25_EINVAL,
+                "The maximum token ID in the query (%lld) is higher than the number of tokens in "
+                "the index.",
+                (long long)mx);
+  return BM25_OK;
+}
+
+// Device copies of the clause rows and the base masks of a host call (the
+// call's own buffers), uploaded on st.
+struct ClauseStage {
+  int32_t* must = nullptr;
+  int32_t* any = nullptr;
+  int32_t* must_not = nullptr;
+  uint32_t* base = nullptr;
+  ~ClauseStage() {
+    hipFree(must);
+    hipFree(any);
+    hipFree(must_not);
+    hipFree(base);
+  }
+  template <class T>
+  static hipError_t up(T** d, const T* src, int64_t n, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    const hipError_t e = hipMalloc(d, sizeof(T) * n);
+    if (e != hipSuccess) return e;
+    return hipMemcpyAsync(*d, src, sizeof(T) * n, hipMemcpyHostToDevice, st);
+  }
+  hipError_t upload(const int32_t* m, int64_t A, const int32_t* a, int64_t B, const int32_t* n,
+                    int64_t N, int64_t M, const uint32_t* b, int64_t Mb, int64_t W, hipStream_t st) {
+    hipError_t e = up(&must, m, M * A, st);
+    if (e == hipSuccess) e = up(&any, a, M * B, st);
+    if (e == hipSuccess) e = up(&must_not, n, M * N, st);
+    if (e == hipSuccess) e = up(&base, b, Mb * W, st);
+    return e;
+  }
+};
+
+}  // namespace
+
+extern "C" {
+
+int bm25_term_masks(bm25_index* h, const int32_t* must, int64_t A, const int32_t* any, int64_t B,
+                    const int32_t* must_not, int64_t N, int64_t M, const uint32_t* base, int64_t Mb,
+                    uint32_t* out_masks) {
+  if (!h) return fail(BM25_EINVAL, "NULL index");
+  int rc = check_clauses(must, A, any, B, must_not, N, M, base, Mb);
+  if (rc) return rc;
+  const int64_t W = (h->ix.n_docs + 31) >> 5;
+  if (M == 0 || W == 0) return BM25_OK;
+  if (!out_masks) return fail(BM25_EINVAL, "NULL output");
+  rc = check_clause_ids(h, 0, must, A, any, B, must_not, N, M);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(h->mu);
+  HIP_TRY(hipSetDevice(h->ix.device), "hipSetDevice");
+  // staging buffers of this call's own (as bm25_score_docs)
+  ClauseStage cs;
+  uint32_t* d_out = nullptr;
+  hipError_t e = cs.upload(must, A, any, B, must_not, N, M, base, Mb, W, h->stream);
+  if (e == hipSuccess) e = hipMalloc(&d_out, sizeof(uint32_t) * M * W);
+  if (e == hipSuccess)
+    e = launch_term_masks(h->ix, cs.must, A, cs.any, B, cs.must_not, N, M, cs.base, Mb, d_out,
+                          h->stream);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(out_masks, d_out, sizeof(uint32_t) * M * W, hipMemcpyDeviceToHost, h->stream);
+  const hipError_t es = hipStreamSynchronize(h->stream);  // (copies in flight read the caller's arrays)
+  hipFree(d_out);
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) return hip_fail(e, "term_masks");
+  return BM25_OK;
+}
+
+int bm25_term_masks_device(bm25_index* h, const int32_t* d_must, int64_t A, const int32_t* d_any,
+                           int64_t B, const int32_t* d_must_not, int64_t N, int64_t M,
+                           const uint32_t* d_base, int64_t Mb, uint32_t* d_out_masks, void* stream) {
+  if (!h) return fail(BM25_EINVAL, "NULL index");
+  const int rc = check_clauses(d_must, A, d_any, B, d_must_not, N, M, d_base, Mb);
+  if (rc) return rc;
+  if (M == 0 || h->ix.n_docs == 0) return BM25_OK;
+  if (!d_out_masks) return fail(BM25_EINVAL, "NULL output");
+  // reads the immutable index arrays only: no workspace, no ordering against
+  // the handle's searches (ws_stream)
+  std::lock_guard<std::mutex> lk(h->mu);
+  HIP_TRY(hipSetDevice(h->ix.device), "hipSetDevice");
+  HIP_TRY(launch_term_masks(h->ix, d_must, A, d_any, B, d_must_not, N, M, d_base, Mb, d_out_masks,
+                            (hipStream_t)stream),
+          "term_masks launch");
+  return BM25_OK;
+}
+
+int bm25_search_boolean(bm25_index* h, const int32_t* queries, int64_t Q, int64_t T, int32_t k,
+                        const int32_t* must, int64_t A, const int32_t* any, int64_t B,
+                        const int32_t* must_not, int64_t N, const uint32_t* base, int64_t Mb,
+                        int32_t* out_docs, float* out_scores) {
+  if (!h) return fail(BM25_EINVAL, "NULL index");
+  if (Q < 0 || T < 0) return fail(BM25_EINVAL, "negative query shape");
+  int rc = check_clauses(must, A, any, B, must_not, N, Q, base, Mb);
+  if (rc) return rc;
+  rc = check_k(h, k);
+  if (rc) return rc;
+  if (Q == 0 || k == 0) return BM25_OK;
+  if (T > 0 && !queries) return fail(BM25_EINVAL, "NULL queries");
+  if (!out_docs || !out_scores) return fail(BM25_EINVAL, "NULL output");
+  int64_t mx = 0;
+  for (int64_t i = 0; i < Q * T; ++i) mx = std::max<int64_t>(mx, queries[i]);
+  rc = check_clause_ids(h, mx, must, A, any, B, must_not, N, Q);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(h->mu);
+  HIP_TRY(hipSetDevice(h->ix.device), "hipSetDevice");
+  rc = ensure_io(h, Q * T, Q * (int64_t)k);
+  if (rc) return rc;
+  // queries per chunk: the masks of one chunk stay on the device, in a buffer
+  // of this call's own of at most 1 GiB (automatic) and at least one query
+  const int64_t W = (h->ix.n_docs + 31) >> 5;  // (k >= 1: n_docs >= 1)
+  int64_t chunk = h->ix.opt.bool_chunk > 0 ? h->ix.opt.bool_chunk
+                                           : std::max<int64_t>(1, ((int64_t)1 << 28) / W);
+  chunk = std::min(chunk, Q);
+  ClauseStage cs;
+  uint32_t* d_masks = nullptr;
+  int32_t* d_qm = nullptr;
+  std::vector<int32_t> ids((size_t)chunk);
+  for (int64_t i = 0; i < chunk; ++i) ids[(size_t)i] = (int32_t)i;
+  hipError_t e = cs.upload(must, A, any, B, must_not, N, Q, base, Mb, W, h->stream);
+  if (e == hipSuccess) e = hipMalloc(&d_masks, sizeof(uint32_t) * chunk * W);
+  if (e == hipSuccess) e = hipMalloc(&d_qm, sizeof(int32_t) * chunk);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(d_qm, ids.data(), sizeof(int32_t) * chunk, hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess && Q * T > 0)
+    e = hipMemcpyAsync(h->d_q, queries, sizeof(int32_t) * Q * T, hipMemcpyHostToDevice, h->stream);
+  int64_t n_dense = 0;
+  for (int64_t q0 = 0; e == hipSuccess && rc == BM25_OK && q0 < Q; q0 += chunk) {
+    const int64_t n = std::min(chunk, Q - q0);
+    e = launch_term_masks(h->ix, cs.must + q0 * A, A, cs.any + q0 * B, B, cs.must_not + q0 * N, N,
+                          n, Mb == Q && Q > 1 ? cs.base + q0 * W : cs.base,
+                          Mb == 0 ? 0 : (Mb == 1 ? 1 : n), d_masks, h->stream);
+    if (e != hipSuccess) break;
+    rc = run_filtered(h, h->d_q + q0 * T, n, T, k, d_masks, n, d_qm, h->d_docs + q0 * k,
+                      h->d_scores + q0 * k, h->stream);
+    n_dense += h->filtered_dense;
+  }
+  h->filtered_dense = n_dense;
+  if (e == hipSuccess && rc == BM25_OK) {
+    e = hipMemcpyAsync(out_docs, h->d_docs, sizeof(int32_t) * Q * k, hipMemcpyDeviceToHost,
+                       h->stream);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(out_scores, h->d_scores, sizeof(float) * Q * k, hipMemcpyDeviceToHost,
+                         h->stream);
+  }
+  const hipError_t es = hipStreamSynchronize(h->stream);  // (copies in flight read the caller's arrays)
+  hipFree(d_masks);
+  hipFree(d_qm);
+  if (rc) return rc;
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) return hip_fail(e, "boolean search");
   return BM25_OK;
 }
 

@@ -90,6 +90,7 @@ struct SearchOpts {
                            // they hold >= kPoolGroupsPerK * k groups
   int filter_tiles = 1;    // filtered search, k <= kMaxK: the tile passes (0: dense score rows
                            // for every query)
+  int bool_chunk = 0;      // boolean search: queries per chunk of masks (0: auto, <= 1 GiB of words)
 };
 
 // What the last search launched (bm25_search_dispatch).
@@ -473,6 +474,20 @@ hipError_t launch_search_filtered(const DevIndex& ix, const int32_t* d_queries, 
                                   const int32_t* d_query_mask, const Workspace& ws,
                                   int32_t* d_docs, float* d_scores, int64_t* n_dense,
                                   hipStream_t stream);
+
+// Boolean term filters as allow-masks (bm25mi_termmask.hip): d_out[M][W] in
+// the layout above, row m = the documents d < n_docs that d_base allows
+// ([Mb][W], Mb = 0 (null: every document), 1 (one row for every mask) or M),
+// that every id >= 0 of d_must[m][A] has, that some id >= 0 of d_any[m][B] has
+// (when it holds one) and that no id >= 0 of d_must_not[m][N] has.  has(t, d):
+// the index stores a posting of (t, d), whatever its value; negative ids are
+// padding, an id >= n_terms is a term that no document has.  Every word of
+// every row is written (bits at or past n_docs as 0), no word at index >= W
+// is read or written.  Reads the index arrays only (no workspace).
+hipError_t launch_term_masks(const DevIndex& ix, const int32_t* d_must, int64_t A,
+                             const int32_t* d_any, int64_t B, const int32_t* d_must_not, int64_t N,
+                             int64_t M, const uint32_t* d_base, int64_t Mb, uint32_t* d_out,
+                             hipStream_t stream);
 
 // Largest token id of [n] device ids (0 if none is positive) into *d_out.
 hipError_t launch_max_token(const int32_t* d_queries, int64_t n, int32_t* d_out,
