@@ -11,6 +11,8 @@
  *   - Return 0 on success, a BM25_E* code otherwise; the message of the last
  *     failure on the calling thread is bm25_last_error().
  *   - Host buffers are C-order numpy-compatible arrays owned by the caller.
+ *     A synchronous call that returns an error has finished reading and
+ *     writing the caller's arrays.
  *   - Device buffers (the *_device entry points) are caller-owned HIP device
  *     allocations on the index's device; `stream` is a hipStream_t passed as
  *     void* (NULL = the legacy default stream).  *_device calls are

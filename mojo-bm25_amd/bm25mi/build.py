@@ -21,6 +21,9 @@ SYNTH_LIB = os.path.join(PKG_DIR, "libbm25synth.so")
 HIP_SOURCES = ["bm25mi_kernels.hip", "bm25mi_large.hip", "bm25mi_build.hip", "bm25mi_sort.hip",
                "bm25mi_dense.hip", "bm25mi_lookup.hip", "bm25mi_filter.hip", "bm25mi_termmask.hip",
                "bm25mi_capi.cpp"]
+# Every header a source may include: an object older than one of them is stale.
+HEADERS = [os.path.join(CSRC, "bm25mi_internal.h"), os.path.join(CSRC, "bm25mi_host.h"),
+           os.path.join(REPO, "include", "bm25mi.h")]
 ARCH = os.environ.get("BM25_OFFLOAD_ARCH", "gfx950")
 
 
@@ -39,7 +42,7 @@ def _run(cmd, verbose):
 
 def build(force: bool = False, verbose: bool = False) -> None:
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    hdrs = [os.path.join(CSRC, "bm25mi_internal.h"), os.path.join(REPO, "include", "bm25mi.h")]
+    hdrs = HEADERS
     lib = os.path.join(PKG_DIR, "libbm25mi.so")
     objdir = os.path.join(PKG_DIR, "_obj")
     os.makedirs(objdir, exist_ok=True)
@@ -84,8 +87,7 @@ def build_asan_check(verbose: bool = False) -> str:
     exe = os.path.join(out, "host_check")
     main = os.path.join(REPO, "tests", "asan", "host_check.cpp")
     srcs = [os.path.join(CSRC, s) for s in HIP_SOURCES] + [main]
-    hdrs = [os.path.join(CSRC, "bm25mi_internal.h"), os.path.join(REPO, "include", "bm25mi.h")]
-    if not _stale(exe, srcs + hdrs):
+    if not _stale(exe, srcs + HEADERS):
         return exe
     flags = [f"--offload-arch={ARCH}", "-O1", "-g", "-std=c++17", "-fPIC", "-w",
              "-Xarch_host", "-fsanitize=address", "-Xarch_host", "-fno-omit-frame-pointer"]

@@ -17,15 +17,16 @@
 #include <string>
 #include <vector>
 
+#include "bm25mi_host.h"
 #include "bm25mi_internal.h"
 
 using namespace bm25mi;
 
 namespace {
-
 thread_local std::string g_err;
+}  // namespace
 
-int fail(int code, const char* fmt, ...) {
+int bm25mi::fail(int code, const char* fmt, ...) {
   char buf[1024];
   va_list ap;
   va_start(ap, fmt);
@@ -35,10 +36,12 @@ int fail(int code, const char* fmt, ...) {
   return code;
 }
 
-int hip_fail(hipError_t e, const char* what) {
+int bm25mi::hip_fail(hipError_t e, const char* what) {
   return fail(e == hipErrorOutOfMemory ? BM25_ENOMEM : BM25_EHIP, "%s: %s (%s)", what,
               hipGetErrorString(e), hipGetErrorName(e));
 }
+
+namespace {
 
 #define HIP_TRY(expr, what)                 \
   do {                                      \
@@ -105,6 +108,35 @@ struct bm25_index {
   int64_t filtered_dense = 0;  // queries of the last filtered search the dense path served
 };
 
+static const OptDesc* find_opt(const char* name) {
+  for (const OptDesc& d : kOpts)
+    if (!strcmp(d.name, name)) return &d;
+  fail(BM25_EINVAL, "unknown option '%s'", name);
+  return nullptr;
+}
+
+int bm25mi::set_opt(SearchOpts& o, const char* name, int64_t v) {
+  if (!name) return fail(BM25_EINVAL, "NULL option name");
+  const OptDesc* d = find_opt(name);
+  if (!d) return BM25_EINVAL;
+  if (v < d->lo || v > d->hi || (d->kind == kOptPow2 && (v & (v - 1)) != 0)) {
+    if (d->msg) return fail(BM25_EINVAL, "%s", d->msg);
+    if (d->kind == kOptBool) return fail(BM25_EINVAL, "%s must be 0 or 1", name);
+    return fail(BM25_EINVAL, d->kind == kOptPow2 ? "%s must be a power of two in %d..%d"
+                                                  : "%s must be in %d..%d", name, d->lo, d->hi);
+  }
+  o.*d->field = (int)v;
+  return BM25_OK;
+}
+
+int bm25mi::get_opt(const SearchOpts& o, const char* name, int64_t* v) {
+  if (!name || !v) return fail(BM25_EINVAL, "NULL argument");
+  const OptDesc* d = find_opt(name);
+  if (!d) return BM25_EINVAL;
+  *v = o.*d->field;
+  return BM25_OK;
+}
+
 namespace {
 
 void free_ws(Workspace& ws) {
@@ -139,105 +171,14 @@ int32_t list_cap_for(const SearchOpts& o, int64_t k) {
 // Options of a new handle: the BM25_* environment (include/bm25mi.h).
 SearchOpts env_opts() {
   SearchOpts o;
-  o.flat = env_int("BM25_FLAT", o.flat) != 0;
-  o.flat_bw = env_int("BM25_FLAT_BW", o.flat_bw);
-  o.items_per_wave = env_int("BM25_ITEMS_PER_WAVE", o.items_per_wave);
-  o.sample_p = env_int("BM25_SAMPLE_P", o.sample_p);
-  o.list_cap = env_int("BM25_LIST_CAP", o.list_cap);
-  o.claim_ch = env_int("BM25_CLAIM_CH", o.claim_ch);
-  o.claim_m = env_int("BM25_CLAIM_M", o.claim_m);
-  o.tile_bound = env_int("BM25_TILE_BOUND", o.tile_bound) != 0;
-  o.theta_bound = env_int("BM25_THETA_BOUND", o.theta_bound) != 0;
-  o.grid_pct = std::min(100, std::max(1, env_int("BM25_GRID_PCT", o.grid_pct)));
-  o.count_skips = env_int("BM25_COUNT_SKIPS", o.count_skips) != 0;
-  o.large_lists = env_int("BM25_LARGE_LISTS", o.large_lists) != 0;
-  o.rest_split = env_int("BM25_REST_SPLIT", o.rest_split) != 0;
-  o.bound_pool = env_int("BM25_BOUND_POOL", o.bound_pool) != 0;
-  o.filter_tiles = env_int("BM25_FILTER_TILES", o.filter_tiles) != 0;
-  o.bool_chunk = std::max(0, env_int("BM25_BOOL_CHUNK", o.bool_chunk));
-  return o;
-}
-
-// Sets one option (EINVAL names the accepted values).
-int set_opt(SearchOpts& o, const char* name, int64_t v) {
-  auto is_pow2 = [](int64_t x) { return x > 0 && (x & (x - 1)) == 0; };
-  if (!name) return fail(BM25_EINVAL, "NULL option name");
-  const std::string n = name;
-  if (n == "flat") {
-    if (v != 0 && v != 1) return fail(BM25_EINVAL, "flat must be 0 or 1");
-    o.flat = (int)v;
-  } else if (n == "flat_bw") {
-    if (v != 0 && !(is_pow2(v) && v <= 8)) return fail(BM25_EINVAL, "flat_bw must be 0, 1, 2, 4 or 8");
-    o.flat_bw = (int)v;
-  } else if (n == "items_per_wave") {
-    if (v < 1 || v > 1024) return fail(BM25_EINVAL, "items_per_wave must be in 1..1024");
-    o.items_per_wave = (int)v;
-  } else if (n == "sample_p") {
-    if (!is_pow2(v) || v > 64) return fail(BM25_EINVAL, "sample_p must be a power of two in 1..64");
-    o.sample_p = (int)v;
-  } else if (n == "list_cap") {
-    if (v < 0 || v > (1 << 20)) return fail(BM25_EINVAL, "list_cap must be in 0..2^20");
-    o.list_cap = (int)v;
-  } else if (n == "claim_ch") {
-    if (v < 1 || v > 64) return fail(BM25_EINVAL, "claim_ch must be in 1..64");
-    o.claim_ch = (int)v;
-  } else if (n == "claim_m") {
-    if (v < 1 || v > kClaimM) return fail(BM25_EINVAL, "claim_m must be in 1..%d", kClaimM);
-    o.claim_m = (int)v;
-  } else if (n == "tile_bound") {
-    if (v != 0 && v != 1) return fail(BM25_EINVAL, "tile_bound must be 0 or 1");
-    o.tile_bound = (int)v;
-  } else if (n == "theta_bound") {
-    if (v != 0 && v != 1) return fail(BM25_EINVAL, "theta_bound must be 0 or 1");
-    o.theta_bound = (int)v;
-  } else if (n == "large_lists") {
-    if (v != 0 && v != 1) return fail(BM25_EINVAL, "large_lists must be 0 or 1");
-    o.large_lists = (int)v;
-  } else if (n == "rest_split") {
-    if (v != 0 && v != 1) return fail(BM25_EINVAL, "rest_split must be 0 or 1");
-    o.rest_split = (int)v;
-  } else if (n == "bound_pool") {
-    if (v != 0 && v != 1) return fail(BM25_EINVAL, "bound_pool must be 0 or 1");
-    o.bound_pool = (int)v;
-  } else if (n == "filter_tiles") {
-    if (v != 0 && v != 1) return fail(BM25_EINVAL, "filter_tiles must be 0 or 1");
-    o.filter_tiles = (int)v;
-  } else if (n == "bool_chunk") {
-    if (v < 0 || v > (1 << 30)) return fail(BM25_EINVAL, "bool_chunk must be in 0..2^30");
-    o.bool_chunk = (int)v;
-  } else if (n == "count_skips") {
-    if (v != 0 && v != 1) return fail(BM25_EINVAL, "count_skips must be 0 or 1");
-    o.count_skips = (int)v;
-  } else if (n == "grid_pct") {
-    if (v < 1 || v > 100) return fail(BM25_EINVAL, "grid_pct must be in 1..100");
-    o.grid_pct = (int)v;
-  } else {
-    return fail(BM25_EINVAL, "unknown option '%s'", name);
+  for (const OptDesc& d : kOpts) {
+    int v = env_int(d.env, o.*d.field);
+    if (d.kind == kOptBool) v = v != 0;
+    if (d.env_clamp >= 1) v = std::max(d.lo, v);
+    if (d.env_clamp >= 2) v = std::min(d.hi, v);
+    o.*d.field = v;
   }
-  return BM25_OK;
-}
-
-int get_opt(const SearchOpts& o, const char* name, int64_t* v) {
-  if (!name || !v) return fail(BM25_EINVAL, "NULL argument");
-  const std::string n = name;
-  if (n == "flat") *v = o.flat;
-  else if (n == "flat_bw") *v = o.flat_bw;
-  else if (n == "items_per_wave") *v = o.items_per_wave;
-  else if (n == "sample_p") *v = o.sample_p;
-  else if (n == "list_cap") *v = o.list_cap;
-  else if (n == "claim_ch") *v = o.claim_ch;
-  else if (n == "claim_m") *v = o.claim_m;
-  else if (n == "tile_bound") *v = o.tile_bound;
-  else if (n == "theta_bound") *v = o.theta_bound;
-  else if (n == "grid_pct") *v = o.grid_pct;
-  else if (n == "count_skips") *v = o.count_skips;
-  else if (n == "large_lists") *v = o.large_lists;
-  else if (n == "rest_split") *v = o.rest_split;
-  else if (n == "bound_pool") *v = o.bound_pool;
-  else if (n == "filter_tiles") *v = o.filter_tiles;
-  else if (n == "bool_chunk") *v = o.bool_chunk;
-  else return fail(BM25_EINVAL, "unknown option '%s'", name);
-  return BM25_OK;
+  return o;
 }
 
 // The workspace for a search of Q queries of T terms at k, enqueued on st.
@@ -296,10 +237,14 @@ int ensure_ws(bm25_index* h, int64_t Q, int64_t T, int k, hipStream_t st) {
   return BM25_OK;
 }
 
+// The handle's persistent staging buffers of the host searches.  A capacity
+// is 0 while its buffer is gone: a failed regrow leaves nothing that the
+// next, smaller call would take for a buffer.
 int ensure_io(bm25_index* h, int64_t q_elems, int64_t out_elems) {
   if (q_elems > h->cap_q_elems) {
     hipFree(h->d_q);
     h->d_q = nullptr;
+    h->cap_q_elems = 0;
     HIP_TRY(hipMalloc(&h->d_q, sizeof(int32_t) * std::max<int64_t>(q_elems, 1)), "hipMalloc(queries)");
     h->cap_q_elems = q_elems;
   }
@@ -308,6 +253,7 @@ int ensure_io(bm25_index* h, int64_t q_elems, int64_t out_elems) {
     hipFree(h->d_scores);
     h->d_docs = nullptr;
     h->d_scores = nullptr;
+    h->cap_out_elems = 0;
     HIP_TRY(hipMalloc(&h->d_docs, sizeof(int32_t) * std::max<int64_t>(out_elems, 1)), "hipMalloc(docs)");
     HIP_TRY(hipMalloc(&h->d_scores, sizeof(float) * std::max<int64_t>(out_elems, 1)), "hipMalloc(scores)");
     h->cap_out_elems = out_elems;
@@ -577,6 +523,42 @@ int check_k(const bm25_index* h, int64_t k, bool shard = false) {
   return BM25_OK;
 }
 
+// max(ids, initial = mx), and the reference's check of it
+// (bm25_native.py:116-121: max(initial=0) >= n_terms -> ValueError).
+int64_t max_token(int64_t mx, const int32_t* ids, int64_t n) {
+  for (int64_t i = 0; i < n; ++i) mx = std::max<int64_t>(mx, ids[i]);
+  return mx;
+}
+
+int check_token_ids(int64_t n_terms, int64_t mx0, const int32_t* ids, int64_t n) {
+  const int64_t mx = max_token(mx0, ids, n);
+  if (mx >= n_terms)
+    return fail(BM25_EINVAL,
+                "The maximum token ID in the query (%lld) is higher than the number of tokens in "
+                "the index.",
+                (long long)mx);
+  return BM25_OK;
+}
+
+// A call's hold on its handle: the handle's mutex, and its device current
+// (rc: hipSetDevice's failure).
+struct Enter {
+  std::lock_guard<std::mutex> lk;
+  int rc;
+  explicit Enter(bm25_index* h) : lk(h->mu), rc(BM25_OK) {
+    const hipError_t e = hipSetDevice(h->ix.device);
+    if (e != hipSuccess) rc = hip_fail(e, "hipSetDevice");
+  }
+};
+
+// A stream of the call's own, destroyed after the HostCall declared below it.
+struct OwnStream {
+  hipStream_t s = nullptr;
+  ~OwnStream() {
+    if (s) hipStreamDestroy(s);
+  }
+};
+
 }  // namespace
 
 extern "C" {
@@ -590,6 +572,9 @@ int bm25_device_count(void) {
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;
   return n;
 }
+
+static int build_index(bm25_index* h, const std::vector<int64_t>& ip, const int32_t* indices,
+                       const float* data);
 
 int bm25_index_create(int device, int64_t n_docs, int64_t n_terms, int64_t nnz,
                       const void* indptr, int indptr_is_i64, const int32_t* indices,
@@ -636,21 +621,34 @@ int bm25_index_create(int device, int64_t n_docs, int64_t n_terms, int64_t nnz,
   ix.doc_offset = doc_offset;
   ix.tile_shift = shift;
   ix.ntiles = ntiles;
-  int32_t* d_indices = nullptr;
-  int32_t* d_err = nullptr;
-  auto cleanup = [&](int rc) {
-    hipFree(d_indices);
-    hipFree(d_err);
-    if (rc != BM25_OK) bm25_index_destroy(h);
-    return rc;
+  const int rc = build_index(h, ip, indices, data);
+  if (rc == BM25_OK) {
+    h->arrays = std::make_shared<IndexArrays>();
+    h->arrays->device = device;
+    h->arrays->p = {ix.indptr, ix.rel, ix.tl_ptr, ix.tl_tile, ix.tl_start, ix.ldoc, ix.val, ix.bmax,
+                    ix.bpool};
+    *out = h;
+  } else {
+    bm25_index_destroy(h);
+  }
+  return rc;
+}
+
+// The device layout of a new handle from the caller's CSC (ip: its indptr
+// as int64), on the handle's new stream.  The arrays it leaves in h->ix are
+// the handle's (bm25_index_destroy frees them after a failure too); the
+// staging buffers are the HostCall's.
+static int build_index(bm25_index* h, const std::vector<int64_t>& ip, const int32_t* indices,
+                       const float* data) {
+  DevIndex& ix = h->ix;
+  const int64_t n_terms = ix.n_terms, nnz = ix.nnz, ntiles = ix.ntiles;
+  HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking), "hipStreamCreate");
+  std::vector<int64_t> cnt;  // (sparse: the tile counts, copied from and to the device)
+  HostCall c(h->stream);
+  // an array of the index's own
+  auto own = [&c](auto** p, int64_t bytes, const char* what) {
+    if (c.ok()) c.run(hipMalloc(p, (size_t)bytes), what);
   };
-  hipError_t e;
-#define TRYC(expr, what)                                          \
-  do {                                                            \
-    e = (expr);                                                   \
-    if (e != hipSuccess) return cleanup(hip_fail(e, what));       \
-  } while (0)
-  TRYC(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking), "hipStreamCreate");
   alloc_report(h);
   // segment table form (DevIndex): BM25_SEGMENTS=dense|sparse; by default the
   // dense V x (ntiles+1) table (O(1) lookups, no per-search table: config 5's
@@ -668,45 +666,37 @@ int bm25_index_create(int device, int64_t n_docs, int64_t n_terms, int64_t nnz,
     else ix.sparse = rel_bytes > 2 * 6 * std::max<int64_t>(nnz, 1) &&
                      rel_bytes > (int64_t)(total_b / 8);
   }
-  TRYC(hipMalloc(&ix.indptr, sizeof(int64_t) * (n_terms + 1)), "hipMalloc(indptr)");
-  if (!ix.sparse)
-    TRYC(hipMalloc(&ix.rel, sizeof(uint32_t) * std::max<int64_t>(rel_elems, 1)), "hipMalloc(rel)");
-  TRYC(hipMalloc(&ix.ldoc, sizeof(uint16_t) * (nnz + kPostingPad)), "hipMalloc(ldoc)");
-  TRYC(hipMalloc(&ix.val, sizeof(float) * (nnz + kPostingPad)), "hipMalloc(val)");
-  TRYC(hipMemsetAsync(ix.ldoc + nnz, 0, sizeof(uint16_t) * kPostingPad, h->stream), "hipMemset");
-  TRYC(hipMemsetAsync(ix.val + nnz, 0, sizeof(float) * kPostingPad, h->stream), "hipMemset");
-  TRYC(hipMalloc(&d_indices, sizeof(int32_t) * std::max<int64_t>(nnz, 1)), "hipMalloc(indices)");
-  TRYC(hipMalloc(&d_err, sizeof(int32_t)), "hipMalloc(err)");
+  own(&ix.indptr, sizeof(int64_t) * (n_terms + 1), "hipMalloc(indptr)");
+  if (!ix.sparse) own(&ix.rel, sizeof(uint32_t) * std::max<int64_t>(rel_elems, 1), "hipMalloc(rel)");
+  own(&ix.ldoc, sizeof(uint16_t) * (nnz + kPostingPad), "hipMalloc(ldoc)");
+  own(&ix.val, sizeof(float) * (nnz + kPostingPad), "hipMalloc(val)");
+  if (c.ok()) c.run(hipMemsetAsync(ix.ldoc + nnz, 0, sizeof(uint16_t) * kPostingPad, h->stream), "hipMemset");
+  if (c.ok()) c.run(hipMemsetAsync(ix.val + nnz, 0, sizeof(float) * kPostingPad, h->stream), "hipMemset");
+  int32_t* d_indices = c.alloc<int32_t>(nnz, "hipMalloc(indices)");
+  int32_t* d_err = c.alloc<int32_t>(1, "hipMalloc(err)");
   h->device_bytes = (int64_t)(sizeof(int64_t) * (n_terms + 1) +
                               (ix.sparse ? 0 : sizeof(uint32_t) * rel_elems) +
                               (sizeof(uint16_t) + sizeof(float)) * nnz);
-  TRYC(hipMemsetAsync(d_err, 0, sizeof(int32_t), h->stream), "hipMemset");
-  TRYC(hipMemcpyAsync(ix.indptr, ip.data(), sizeof(int64_t) * (n_terms + 1), hipMemcpyHostToDevice, h->stream), "H2D indptr");
-  if (nnz > 0) {
-    TRYC(hipMemcpyAsync(d_indices, indices, sizeof(int32_t) * nnz, hipMemcpyHostToDevice, h->stream), "H2D indices");
-    TRYC(hipMemcpyAsync(ix.val, data, sizeof(float) * nnz, hipMemcpyHostToDevice, h->stream), "H2D data");
-  }
+  if (c.ok()) c.run(hipMemsetAsync(d_err, 0, sizeof(int32_t), h->stream), "hipMemset");
+  c.upload_to(ix.indptr, ip.data(), n_terms + 1, "H2D indptr");
+  c.upload_to(d_indices, indices, nnz, "H2D indices");
+  c.upload_to(ix.val, data, nnz, "H2D data");
   if (!ix.sparse) {
-    TRYC(launch_build_tables(ix, d_indices, d_err, h->stream), "build_tables launch");
+    if (c.ok()) c.run(launch_build_tables(ix, d_indices, d_err, h->stream), "build_tables launch");
   } else {  // tile lists: count per term, scan on the host, fill
-    int64_t* d_cnt = nullptr;
-    TRYC(hipMalloc(&d_cnt, sizeof(int64_t) * std::max<int64_t>(n_terms, 1)), "hipMalloc(cnt)");
-    std::vector<int64_t> cnt(n_terms + 1, 0);
-    e = launch_count_tiles(ix, d_indices, d_cnt, d_err, h->stream);
-    if (e == hipSuccess && n_terms > 0)
-      e = hipMemcpyAsync(cnt.data() + 1, d_cnt, sizeof(int64_t) * n_terms, hipMemcpyDeviceToHost,
-                         h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    hipFree(d_cnt);
-    if (e != hipSuccess) return cleanup(hip_fail(e, "count_tiles"));
+    int64_t* d_cnt = c.alloc<int64_t>(n_terms, "hipMalloc(cnt)");
+    cnt.assign(n_terms + 1, 0);
+    if (c.ok()) c.run(launch_count_tiles(ix, d_indices, d_cnt, d_err, h->stream), "count_tiles");
+    c.download(cnt.data() + 1, d_cnt, n_terms, "count_tiles");
+    if (c.ok()) c.run(hipStreamSynchronize(h->stream), "count_tiles");
     for (int64_t t = 0; t < n_terms; ++t) cnt[t + 1] += cnt[t];
     ix.n_pairs = cnt[n_terms];
-    TRYC(hipMalloc(&ix.tl_ptr, sizeof(int64_t) * (n_terms + 1)), "hipMalloc(tl_ptr)");
-    TRYC(hipMalloc(&ix.tl_tile, sizeof(uint16_t) * std::max<int64_t>(ix.n_pairs, 1)), "hipMalloc(tl_tile)");
-    TRYC(hipMalloc(&ix.tl_start, sizeof(uint32_t) * std::max<int64_t>(ix.n_pairs, 1)), "hipMalloc(tl_start)");
-    TRYC(hipMemcpyAsync(ix.tl_ptr, cnt.data(), sizeof(int64_t) * (n_terms + 1), hipMemcpyHostToDevice, h->stream), "H2D tl_ptr");
-    TRYC(launch_fill_tiles(ix, d_indices, h->stream), "fill_tiles launch");
-    TRYC(hipStreamSynchronize(h->stream), "fill_tiles");
+    own(&ix.tl_ptr, sizeof(int64_t) * (n_terms + 1), "hipMalloc(tl_ptr)");
+    own(&ix.tl_tile, sizeof(uint16_t) * std::max<int64_t>(ix.n_pairs, 1), "hipMalloc(tl_tile)");
+    own(&ix.tl_start, sizeof(uint32_t) * std::max<int64_t>(ix.n_pairs, 1), "hipMalloc(tl_start)");
+    c.upload_to(ix.tl_ptr, cnt.data(), n_terms + 1, "H2D tl_ptr");
+    if (c.ok()) c.run(launch_fill_tiles(ix, d_indices, h->stream), "fill_tiles launch");
+    if (c.ok()) c.run(hipStreamSynchronize(h->stream), "fill_tiles");
     h->device_bytes += (int64_t)(sizeof(int64_t) * (n_terms + 1) +
                                  (sizeof(uint16_t) + sizeof(uint32_t)) * ix.n_pairs);
   }
@@ -719,16 +709,16 @@ int bm25_index_create(int device, int64_t n_docs, int64_t n_terms, int64_t nnz,
     ix.nonneg = data[p] == 0.0f || data[p] >= 1.17549435e-38f;
   // tile bounds of the REST pass (dense table, non-negative index); without
   // the memory the search simply runs without them
-  if (!ix.sparse && ix.nonneg && n_terms > 0 && ntiles > 0) {
+  if (c.ok() && !ix.sparse && ix.nonneg && n_terms > 0 && ntiles > 0) {
     if (hipMalloc(&ix.bmax, sizeof(uint16_t) * n_terms * bmax_stride(ntiles)) == hipSuccess) {
-      TRYC(launch_build_bmax(ix, h->stream), "build_bmax launch");
+      c.run(launch_build_bmax(ix, h->stream), "build_bmax launch");
       h->device_bytes += (int64_t)(sizeof(uint16_t) * n_terms * bmax_stride(ntiles));
       // the pooled copy of the threshold kernel (a quarter of the bytes; optional)
       const int64_t ps = bmax_stride((ntiles + kPool - 1) / kPool);
-      if (hipMalloc(&ix.bpool, sizeof(uint16_t) * n_terms * ps) == hipSuccess) {
+      if (c.ok() && hipMalloc(&ix.bpool, sizeof(uint16_t) * n_terms * ps) == hipSuccess) {
         ix.pstride = ps;
-        TRYC(launch_pool_bounds(ix.bmax, n_terms, bmax_stride(ntiles), ix.bpool, ps, h->stream),
-             "pool_bounds launch");
+        c.run(launch_pool_bounds(ix.bmax, n_terms, bmax_stride(ntiles), ix.bpool, ps, h->stream),
+              "pool_bounds launch");
         h->device_bytes += (int64_t)(sizeof(uint16_t) * n_terms * ps);
       } else {
         (void)hipGetLastError();
@@ -740,19 +730,14 @@ int bm25_index_create(int device, int64_t n_docs, int64_t n_terms, int64_t nnz,
     }
   }
   int32_t herr = 0;
-  TRYC(hipMemcpyAsync(&herr, d_err, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream), "D2H err");
-  TRYC(hipStreamSynchronize(h->stream), "build sync");
-#undef TRYC
+  c.download(&herr, d_err, 1, "D2H err");
+  const int rc = c.finish("build sync");
+  if (rc) return rc;
   if (herr)
-    return cleanup(fail(BM25_EINVAL,
-                        "indices must be sorted, unique and in [0, n_docs) within every column "
-                        "(canonical CSC)"));
-  h->arrays = std::make_shared<IndexArrays>();
-  h->arrays->device = device;
-  h->arrays->p = {ix.indptr, ix.rel, ix.tl_ptr, ix.tl_tile, ix.tl_start, ix.ldoc, ix.val, ix.bmax,
-                  ix.bpool};
-  *out = h;
-  return cleanup(BM25_OK);
+    return fail(BM25_EINVAL,
+                "indices must be sorted, unique and in [0, n_docs) within every column "
+                "(canonical CSC)");
+  return BM25_OK;
 }
 
 int bm25_index_destroy(bm25_index* h) {
@@ -858,26 +843,18 @@ int bm25_search(bm25_index* h, const int32_t* queries, int64_t Q, int64_t T, int
   if (Q == 0 || k == 0) return BM25_OK;
   if (T > 0 && !queries) return fail(BM25_EINVAL, "NULL queries");
   if (!out_docs || !out_scores) return fail(BM25_EINVAL, "NULL output");
-  // bm25_native.py:116-121: max(initial=0) >= n_terms -> ValueError
-  int64_t mx = 0;
-  for (int64_t i = 0; i < Q * T; ++i) mx = std::max<int64_t>(mx, queries[i]);
-  if (mx >= h->ix.n_terms)
-    return fail(BM25_EINVAL,
-                "The maximum token ID in the query (%lld) is higher than the number of tokens in "
-                "the index.",
-                (long long)mx);
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIP_TRY(hipSetDevice(h->ix.device), "hipSetDevice");
+  rc = check_token_ids(h->ix.n_terms, 0, queries, Q * T);
+  if (rc) return rc;
+  Enter in(h);
+  if (in.rc) return in.rc;
   rc = ensure_io(h, Q * T, Q * (int64_t)k);
   if (rc) return rc;
-  if (Q * T > 0)
-    HIP_TRY(hipMemcpyAsync(h->d_q, queries, sizeof(int32_t) * Q * T, hipMemcpyHostToDevice, h->stream), "H2D queries");
-  rc = run_search(h, h->d_q, Q, T, k, h->d_docs, h->d_scores, h->stream);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(out_docs, h->d_docs, sizeof(int32_t) * Q * k, hipMemcpyDeviceToHost, h->stream), "D2H docs");
-  HIP_TRY(hipMemcpyAsync(out_scores, h->d_scores, sizeof(float) * Q * k, hipMemcpyDeviceToHost, h->stream), "D2H scores");
-  HIP_TRY(hipStreamSynchronize(h->stream), "search sync");
-  return BM25_OK;
+  HostCall c(h->stream);
+  c.upload_to(h->d_q, queries, Q * T, "H2D queries");
+  if (c.ok()) c.hold(run_search(h, h->d_q, Q, T, k, h->d_docs, h->d_scores, h->stream));
+  c.download(out_docs, h->d_docs, Q * k, "D2H docs");
+  c.download(out_scores, h->d_scores, Q * k, "D2H scores");
+  return c.finish("search sync");
 }
 
 int bm25_search_device(bm25_index* h, const int32_t* d_queries, int64_t Q, int64_t T, int32_t k,
@@ -887,8 +864,8 @@ int bm25_search_device(bm25_index* h, const int32_t* d_queries, int64_t Q, int64
   int rc = check_k(h, k);
   if (rc) return rc;
   if (Q == 0 || k == 0) return BM25_OK;
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIP_TRY(hipSetDevice(h->ix.device), "hipSetDevice");
+  Enter in(h);
+  if (in.rc) return in.rc;
   return run_search(h, d_queries, Q, T, k, d_docs, d_scores, (hipStream_t)stream);
 }
 
@@ -905,57 +882,30 @@ int bm25_search_filtered(bm25_index* h, const int32_t* queries, int64_t Q, int64
   if (M == 0 && !query_mask)
     return fail(BM25_EINVAL, "no masks: query_mask must name -1 (no filter) for every query");
   if (!out_docs || !out_scores) return fail(BM25_EINVAL, "NULL output");
-  // bm25_native.py:116-121: max(initial=0) >= n_terms -> ValueError
-  int64_t mx = 0;
-  for (int64_t i = 0; i < Q * T; ++i) mx = std::max<int64_t>(mx, queries[i]);
-  if (mx >= h->ix.n_terms)
-    return fail(BM25_EINVAL,
-                "The maximum token ID in the query (%lld) is higher than the number of tokens in "
-                "the index.",
-                (long long)mx);
+  rc = check_token_ids(h->ix.n_terms, 0, queries, Q * T);
+  if (rc) return rc;
   if (query_mask)
     for (int64_t i = 0; i < Q; ++i)
       if (query_mask[i] < -1 || query_mask[i] >= M)
         return fail(BM25_EINVAL, "query_mask[%lld] = %d is outside [-1, %lld)", (long long)i,
                     query_mask[i], (long long)M);
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIP_TRY(hipSetDevice(h->ix.device), "hipSetDevice");
+  Enter in(h);
+  if (in.rc) return in.rc;
   rc = ensure_io(h, Q * T, Q * (int64_t)k);
   if (rc) return rc;
   // the masks and mask ids: staging buffers of this call's own
   const int64_t W = (h->ix.n_docs + 31) >> 5;
-  uint32_t* d_masks = nullptr;
-  int32_t* d_qm = nullptr;
-  hipError_t e = hipSuccess;
-  if (M > 0) e = hipMalloc(&d_masks, sizeof(uint32_t) * M * W);
-  if (e == hipSuccess && query_mask) e = hipMalloc(&d_qm, sizeof(int32_t) * Q);
-  if (e == hipSuccess && M > 0)
-    e = hipMemcpyAsync(d_masks, masks, sizeof(uint32_t) * M * W, hipMemcpyHostToDevice, h->stream);
-  if (e == hipSuccess && query_mask)
-    e = hipMemcpyAsync(d_qm, query_mask, sizeof(int32_t) * Q, hipMemcpyHostToDevice, h->stream);
-  if (e == hipSuccess && Q * T > 0)
-    e = hipMemcpyAsync(h->d_q, queries, sizeof(int32_t) * Q * T, hipMemcpyHostToDevice, h->stream);
-  if (e != hipSuccess) {
-    hipStreamSynchronize(h->stream);  // (copies in flight read the caller's arrays)
-    hipFree(d_masks);
-    hipFree(d_qm);
-    return hip_fail(e, "filtered search staging");
-  }
-  rc = run_filtered(h, h->d_q, Q, T, k, d_masks, M, d_qm, h->d_docs, h->d_scores, h->stream);
-  if (rc == BM25_OK) {
-    e = hipMemcpyAsync(out_docs, h->d_docs, sizeof(int32_t) * Q * k, hipMemcpyDeviceToHost,
-                       h->stream);
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(out_scores, h->d_scores, sizeof(float) * Q * k, hipMemcpyDeviceToHost,
-                         h->stream);
-  }
-  const hipError_t es = hipStreamSynchronize(h->stream);
-  hipFree(d_masks);
-  hipFree(d_qm);
-  if (rc) return rc;
-  if (e == hipSuccess) e = es;
-  if (e != hipSuccess) return hip_fail(e, "filtered search");
-  return BM25_OK;
+  HostCall c(h->stream);
+  uint32_t* d_masks = M > 0 ? c.alloc<uint32_t>(M * W) : nullptr;
+  int32_t* d_qm = query_mask ? c.alloc<int32_t>(Q) : nullptr;
+  c.upload_to(d_masks, masks, M * W);
+  if (query_mask) c.upload_to(d_qm, query_mask, Q);
+  c.upload_to(h->d_q, queries, Q * T);
+  if (!c.ok()) return c.finish("filtered search staging");
+  c.hold(run_filtered(h, h->d_q, Q, T, k, d_masks, M, d_qm, h->d_docs, h->d_scores, h->stream));
+  c.download(out_docs, h->d_docs, Q * k);
+  c.download(out_scores, h->d_scores, Q * k);
+  return c.finish("filtered search");
 }
 
 int bm25_search_filtered_device(bm25_index* h, const int32_t* d_queries, int64_t Q, int64_t T,
@@ -967,8 +917,8 @@ int bm25_search_filtered_device(bm25_index* h, const int32_t* d_queries, int64_t
   int rc = check_k(h, k);
   if (rc) return rc;
   if (Q == 0 || k == 0) return BM25_OK;
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIP_TRY(hipSetDevice(h->ix.device), "hipSetDevice");
+  Enter in(h);
+  if (in.rc) return in.rc;
   return run_filtered(h, d_queries, Q, T, k, d_masks, M, d_query_mask, d_docs, d_scores,
                       (hipStream_t)stream);
 }
@@ -977,8 +927,8 @@ int bm25_search_filtered_stats(bm25_index* h, int64_t* out, int32_t n) {
   if (!h) return fail(BM25_EINVAL, "NULL index");
   if (!out) return fail(BM25_EINVAL, "NULL argument");
   if (n < 1 || n > 3) return fail(BM25_EINVAL, "n=%d must be in 1..3", n);
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIP_TRY(hipSetDevice(h->ix.device), "hipSetDevice");
+  Enter in(h);
+  if (in.rc) return in.rc;
   int32_t cnt[kCounters] = {};
   read_counters(h, cnt);
   // (counters [5] and [3]: pass A's skipped pairs, pass B's re-scored pairs)
@@ -1008,49 +958,12 @@ int check_clauses(const void* must, int64_t A, const void* any, int64_t B, const
   return BM25_OK;
 }
 
-// bm25_native.py:116-121 over the clause ids: max(initial = mx) >= n_terms -> ValueError
+// check_token_ids over the clause ids: max(initial = mx) >= n_terms -> ValueError
 int check_clause_ids(const bm25_index* h, int64_t mx, const int32_t* must, int64_t A,
                      const int32_t* any, int64_t B, const int32_t* must_not, int64_t N, int64_t M) {
-  for (int64_t i = 0; i < M * A; ++i) mx = std::max<int64_t>(mx, must[i]);
-  for (int64_t i = 0; i < M * B; ++i) mx = std::max<int64_t>(mx, any[i]);
-  for (int64_t i = 0; i < M * N; ++i) mx = std::max<int64_t>(mx, must_not[i]);
-  if (mx >= h->ix.n_terms)
-    return fail(BM25_EINVAL,
-                "The maximum token ID in the query (%lld) is higher than the number of tokens in "
-                "the index.",
-                (long long)mx);
-  return BM25_OK;
+  mx = max_token(max_token(mx, must, M * A), any, M * B);
+  return check_token_ids(h->ix.n_terms, mx, must_not, M * N);
 }
-
-// Device copies of the clause rows and the base masks of a host call (the
-// call's own buffers), uploaded on st.
-struct ClauseStage {
-  int32_t* must = nullptr;
-  int32_t* any = nullptr;
-  int32_t* must_not = nullptr;
-  uint32_t* base = nullptr;
-  ~ClauseStage() {
-    hipFree(must);
-    hipFree(any);
-    hipFree(must_not);
-    hipFree(base);
-  }
-  template <class T>
-  static hipError_t up(T** d, const T* src, int64_t n, hipStream_t st) {
-    if (n <= 0) return hipSuccess;
-    const hipError_t e = hipMalloc(d, sizeof(T) * n);
-    if (e != hipSuccess) return e;
-    return hipMemcpyAsync(*d, src, sizeof(T) * n, hipMemcpyHostToDevice, st);
-  }
-  hipError_t upload(const int32_t* m, int64_t A, const int32_t* a, int64_t B, const int32_t* n,
-                    int64_t N, int64_t M, const uint32_t* b, int64_t Mb, int64_t W, hipStream_t st) {
-    hipError_t e = up(&must, m, M * A, st);
-    if (e == hipSuccess) e = up(&any, a, M * B, st);
-    if (e == hipSuccess) e = up(&must_not, n, M * N, st);
-    if (e == hipSuccess) e = up(&base, b, Mb * W, st);
-    return e;
-  }
-};
 
 }  // namespace
 
@@ -1067,23 +980,19 @@ int bm25_term_masks(bm25_index* h, const int32_t* must, int64_t A, const int32_t
   if (!out_masks) return fail(BM25_EINVAL, "NULL output");
   rc = check_clause_ids(h, 0, must, A, any, B, must_not, N, M);
   if (rc) return rc;
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIP_TRY(hipSetDevice(h->ix.device), "hipSetDevice");
+  Enter in(h);
+  if (in.rc) return in.rc;
   // staging buffers of this call's own (as bm25_score_docs)
-  ClauseStage cs;
-  uint32_t* d_out = nullptr;
-  hipError_t e = cs.upload(must, A, any, B, must_not, N, M, base, Mb, W, h->stream);
-  if (e == hipSuccess) e = hipMalloc(&d_out, sizeof(uint32_t) * M * W);
-  if (e == hipSuccess)
-    e = launch_term_masks(h->ix, cs.must, A, cs.any, B, cs.must_not, N, M, cs.base, Mb, d_out,
-                          h->stream);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(out_masks, d_out, sizeof(uint32_t) * M * W, hipMemcpyDeviceToHost, h->stream);
-  const hipError_t es = hipStreamSynchronize(h->stream);  // (copies in flight read the caller's arrays)
-  hipFree(d_out);
-  if (e == hipSuccess) e = es;
-  if (e != hipSuccess) return hip_fail(e, "term_masks");
-  return BM25_OK;
+  HostCall c(h->stream);
+  const int32_t* d_must = c.upload(must, M * A);
+  const int32_t* d_any = c.upload(any, M * B);
+  const int32_t* d_not = c.upload(must_not, M * N);
+  const uint32_t* d_base = c.upload(base, Mb * W);
+  uint32_t* d_out = c.alloc<uint32_t>(M * W);
+  if (c.ok())
+    c.run(launch_term_masks(h->ix, d_must, A, d_any, B, d_not, N, M, d_base, Mb, d_out, h->stream));
+  c.download(out_masks, d_out, M * W);
+  return c.finish("term_masks");
 }
 
 int bm25_term_masks_device(bm25_index* h, const int32_t* d_must, int64_t A, const int32_t* d_any,
@@ -1096,8 +1005,8 @@ int bm25_term_masks_device(bm25_index* h, const int32_t* d_must, int64_t A, cons
   if (!d_out_masks) return fail(BM25_EINVAL, "NULL output");
   // reads the immutable index arrays only: no workspace, no ordering against
   // the handle's searches (ws_stream)
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIP_TRY(hipSetDevice(h->ix.device), "hipSetDevice");
+  Enter in(h);
+  if (in.rc) return in.rc;
   HIP_TRY(launch_term_masks(h->ix, d_must, A, d_any, B, d_must_not, N, M, d_base, Mb, d_out_masks,
                             (hipStream_t)stream),
           "term_masks launch");
@@ -1117,12 +1026,10 @@ int bm25_search_boolean(bm25_index* h, const int32_t* queries, int64_t Q, int64_
   if (Q == 0 || k == 0) return BM25_OK;
   if (T > 0 && !queries) return fail(BM25_EINVAL, "NULL queries");
   if (!out_docs || !out_scores) return fail(BM25_EINVAL, "NULL output");
-  int64_t mx = 0;
-  for (int64_t i = 0; i < Q * T; ++i) mx = std::max<int64_t>(mx, queries[i]);
-  rc = check_clause_ids(h, mx, must, A, any, B, must_not, N, Q);
+  rc = check_clause_ids(h, max_token(0, queries, Q * T), must, A, any, B, must_not, N, Q);
   if (rc) return rc;
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIP_TRY(hipSetDevice(h->ix.device), "hipSetDevice");
+  Enter in(h);
+  if (in.rc) return in.rc;
   rc = ensure_io(h, Q * T, Q * (int64_t)k);
   if (rc) return rc;
   // queries per chunk: the masks of one chunk stay on the device, in a buffer
@@ -1131,44 +1038,32 @@ int bm25_search_boolean(bm25_index* h, const int32_t* queries, int64_t Q, int64_
   int64_t chunk = h->ix.opt.bool_chunk > 0 ? h->ix.opt.bool_chunk
                                            : std::max<int64_t>(1, ((int64_t)1 << 28) / W);
   chunk = std::min(chunk, Q);
-  ClauseStage cs;
-  uint32_t* d_masks = nullptr;
-  int32_t* d_qm = nullptr;
   std::vector<int32_t> ids((size_t)chunk);
   for (int64_t i = 0; i < chunk; ++i) ids[(size_t)i] = (int32_t)i;
-  hipError_t e = cs.upload(must, A, any, B, must_not, N, Q, base, Mb, W, h->stream);
-  if (e == hipSuccess) e = hipMalloc(&d_masks, sizeof(uint32_t) * chunk * W);
-  if (e == hipSuccess) e = hipMalloc(&d_qm, sizeof(int32_t) * chunk);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(d_qm, ids.data(), sizeof(int32_t) * chunk, hipMemcpyHostToDevice, h->stream);
-  if (e == hipSuccess && Q * T > 0)
-    e = hipMemcpyAsync(h->d_q, queries, sizeof(int32_t) * Q * T, hipMemcpyHostToDevice, h->stream);
+  HostCall c(h->stream);
+  const int32_t* d_must = c.upload(must, Q * A);
+  const int32_t* d_any = c.upload(any, Q * B);
+  const int32_t* d_not = c.upload(must_not, Q * N);
+  const uint32_t* d_base = c.upload(base, Mb * W);
+  uint32_t* d_masks = c.alloc<uint32_t>(chunk * W);
+  int32_t* d_qm = c.alloc<int32_t>(chunk);
+  c.upload_to(d_qm, ids.data(), chunk);
+  c.upload_to(h->d_q, queries, Q * T);
   int64_t n_dense = 0;
-  for (int64_t q0 = 0; e == hipSuccess && rc == BM25_OK && q0 < Q; q0 += chunk) {
+  for (int64_t q0 = 0; c.ok() && q0 < Q; q0 += chunk) {
     const int64_t n = std::min(chunk, Q - q0);
-    e = launch_term_masks(h->ix, cs.must + q0 * A, A, cs.any + q0 * B, B, cs.must_not + q0 * N, N,
-                          n, Mb == Q && Q > 1 ? cs.base + q0 * W : cs.base,
-                          Mb == 0 ? 0 : (Mb == 1 ? 1 : n), d_masks, h->stream);
-    if (e != hipSuccess) break;
-    rc = run_filtered(h, h->d_q + q0 * T, n, T, k, d_masks, n, d_qm, h->d_docs + q0 * k,
-                      h->d_scores + q0 * k, h->stream);
+    c.run(launch_term_masks(h->ix, d_must + q0 * A, A, d_any + q0 * B, B, d_not + q0 * N, N, n,
+                            Mb == Q && Q > 1 ? d_base + q0 * W : d_base,
+                            Mb == 0 ? 0 : (Mb == 1 ? 1 : n), d_masks, h->stream));
+    if (!c.ok()) break;
+    c.hold(run_filtered(h, h->d_q + q0 * T, n, T, k, d_masks, n, d_qm, h->d_docs + q0 * k,
+                        h->d_scores + q0 * k, h->stream));
     n_dense += h->filtered_dense;
   }
   h->filtered_dense = n_dense;
-  if (e == hipSuccess && rc == BM25_OK) {
-    e = hipMemcpyAsync(out_docs, h->d_docs, sizeof(int32_t) * Q * k, hipMemcpyDeviceToHost,
-                       h->stream);
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(out_scores, h->d_scores, sizeof(float) * Q * k, hipMemcpyDeviceToHost,
-                         h->stream);
-  }
-  const hipError_t es = hipStreamSynchronize(h->stream);  // (copies in flight read the caller's arrays)
-  hipFree(d_masks);
-  hipFree(d_qm);
-  if (rc) return rc;
-  if (e == hipSuccess) e = es;
-  if (e != hipSuccess) return hip_fail(e, "boolean search");
-  return BM25_OK;
+  c.download(out_docs, h->d_docs, Q * k);
+  c.download(out_scores, h->d_scores, Q * k);
+  return c.finish("boolean search");
 }
 
 int bm25_index_bounds_export(bm25_index* h, uint16_t* d_out, int64_t stride, void* stream) {
@@ -1274,8 +1169,8 @@ int bm25_max_token_device(bm25_index* h, const int32_t* d_queries, int64_t Q, in
                           int32_t* max_token, void* stream) {
   if (!h || !max_token) return fail(BM25_EINVAL, "NULL argument");
   if (Q < 0 || T < 0) return fail(BM25_EINVAL, "negative query shape");
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIP_TRY(hipSetDevice(h->ix.device), "hipSetDevice");
+  Enter in(h);
+  if (in.rc) return in.rc;
   if (!h->d_maxtok) HIP_TRY(hipMalloc(&h->d_maxtok, sizeof(int32_t)), "hipMalloc");
   const hipStream_t st = (hipStream_t)stream;
   HIP_TRY(launch_max_token(d_queries, Q * T, h->d_maxtok, st), "max_token_kernel");
@@ -1311,8 +1206,8 @@ int bm25_search_sample_device(bm25_index* h, const int32_t* d_queries, int64_t Q
   int rc = check_k(h, k, true);
   if (rc) return rc;
   if (Q == 0 || k == 0 || k > kMaxK) return BM25_OK;  // k > kMaxK: no sample half
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIP_TRY(hipSetDevice(h->ix.device), "hipSetDevice");
+  Enter in(h);
+  if (in.rc) return in.rc;
   const hipStream_t st = (hipStream_t)stream;
   rc = ensure_ws(h, Q, T, k, st);
   if (rc) return rc;
@@ -1342,8 +1237,8 @@ static int finish_impl(bm25_index* h, const int32_t* d_queries, int64_t Q, int64
   int rc = check_k(h, k, true);
   if (rc) return rc;
   if (Q == 0 || k == 0) return BM25_OK;
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIP_TRY(hipSetDevice(h->ix.device), "hipSetDevice");
+  Enter in(h);
+  if (in.rc) return in.rc;
   for (hipEvent_t& e : h->ev_split)
     if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate");
   // st_sel continues after everything enqueued on st (an event; none if equal)
@@ -1435,65 +1330,42 @@ int bm25_build_scores(int device, int64_t n_docs, int64_t n_terms, int64_t n_tri
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(BM25_EHIP, "no HIP device available");
   if (device < 0 || device >= ndev) return fail(BM25_EINVAL, "device %d out of range (%d visible)", device, ndev);
   HIP_TRY(hipSetDevice(device), "hipSetDevice");
-  const size_t n = (size_t)std::max<int64_t>(n_triples, 1);
-  int32_t *d_docs = nullptr, *d_terms = nullptr, *d_dl = nullptr, *d_ix = nullptr, *d_err = nullptr;
-  float *d_tf = nullptr, *d_idf = nullptr, *d_dt = nullptr;
-  double* d_dt64 = nullptr;
-  int64_t* d_ip = nullptr;
-  hipStream_t st = nullptr;
-  auto cleanup = [&](int rc) {
-    if (st) hipStreamSynchronize(st);
-    for (void* p : {(void*)d_docs, (void*)d_terms, (void*)d_dl, (void*)d_ix, (void*)d_err,
-                    (void*)d_tf, (void*)d_idf, (void*)d_dt, (void*)d_dt64, (void*)d_ip})
-      hipFree(p);
-    if (st) hipStreamDestroy(st);
-    return rc;
-  };
-  hipError_t e;
-#define TRYB(expr, what)                                    \
-  do {                                                      \
-    e = (expr);                                             \
-    if (e != hipSuccess) return cleanup(hip_fail(e, what)); \
-  } while (0)
-  TRYB(hipStreamCreateWithFlags(&st, hipStreamNonBlocking), "hipStreamCreate");
-  TRYB(hipMalloc(&d_docs, sizeof(int32_t) * n), "hipMalloc(docs)");
-  TRYB(hipMalloc(&d_terms, sizeof(int32_t) * n), "hipMalloc(terms)");
-  TRYB(hipMalloc(&d_tf, sizeof(float) * n), "hipMalloc(tf)");
-  TRYB(hipMalloc(&d_dl, sizeof(int32_t) * std::max<int64_t>(n_docs, 1)), "hipMalloc(doc_len)");
-  TRYB(hipMalloc(&d_ix, sizeof(int32_t) * n), "hipMalloc(indices)");
-  TRYB(hipMalloc(&d_dt, sizeof(float) * n), "hipMalloc(data)");
-  TRYB(hipMalloc(&d_ip, sizeof(int64_t) * (n_terms + 1)), "hipMalloc(indptr)");
-  TRYB(hipMalloc(&d_err, sizeof(int32_t)), "hipMalloc(err)");
-  if (out_data64) TRYB(hipMalloc(&d_dt64, sizeof(double) * n), "hipMalloc(data64)");
-  if (idf) {
-    TRYB(hipMalloc(&d_idf, sizeof(float) * std::max<int64_t>(n_terms, 1)), "hipMalloc(idf)");
-    TRYB(hipMemcpyAsync(d_idf, idf, sizeof(float) * n_terms, hipMemcpyHostToDevice, st), "H2D idf");
-  }
-  TRYB(hipMemsetAsync(d_err, 0, sizeof(int32_t), st), "hipMemset");
-  if (n_triples > 0) {
-    TRYB(hipMemcpyAsync(d_docs, docs, sizeof(int32_t) * n_triples, hipMemcpyHostToDevice, st), "H2D docs");
-    TRYB(hipMemcpyAsync(d_terms, terms, sizeof(int32_t) * n_triples, hipMemcpyHostToDevice, st), "H2D terms");
-    TRYB(hipMemcpyAsync(d_tf, tfs, sizeof(float) * n_triples, hipMemcpyHostToDevice, st), "H2D tf");
-    TRYB(hipMemcpyAsync(d_dl, doc_len, sizeof(int32_t) * n_docs, hipMemcpyHostToDevice, st), "H2D doc_len");
-  }
-  TRYB(build_scores(n_docs, n_terms, n_triples, d_docs, d_terms, d_tf, d_dl, avgdl, k1, b, method,
-                    d_idf, d_ip, d_ix, d_dt, d_dt64, d_err, st), "build_scores");
+  const int64_t n = n_triples;
+  OwnStream own;
+  HIP_TRY(hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking), "hipStreamCreate");
+  const hipStream_t st = own.s;
+  HostCall c(st);
+  int32_t* d_docs = c.alloc<int32_t>(n, "hipMalloc(docs)");
+  int32_t* d_terms = c.alloc<int32_t>(n, "hipMalloc(terms)");
+  float* d_tf = c.alloc<float>(n, "hipMalloc(tf)");
+  int32_t* d_dl = c.alloc<int32_t>(n_docs, "hipMalloc(doc_len)");
+  int32_t* d_ix = c.alloc<int32_t>(n, "hipMalloc(indices)");
+  float* d_dt = c.alloc<float>(n, "hipMalloc(data)");
+  int64_t* d_ip = c.alloc<int64_t>(n_terms + 1, "hipMalloc(indptr)");
+  int32_t* d_err = c.alloc<int32_t>(1, "hipMalloc(err)");
+  double* d_dt64 = out_data64 ? c.alloc<double>(n, "hipMalloc(data64)") : nullptr;
+  float* d_idf = idf ? c.alloc<float>(n_terms, "hipMalloc(idf)") : nullptr;
+  if (idf) c.upload_to(d_idf, idf, n_terms, "H2D idf");
+  if (c.ok()) c.run(hipMemsetAsync(d_err, 0, sizeof(int32_t), st), "hipMemset");
+  c.upload_to(d_docs, docs, n, "H2D docs");
+  c.upload_to(d_terms, terms, n, "H2D terms");
+  c.upload_to(d_tf, tfs, n, "H2D tf");
+  if (n > 0) c.upload_to(d_dl, doc_len, n_docs, "H2D doc_len");
+  if (c.ok())
+    c.run(build_scores(n_docs, n_terms, n_triples, d_docs, d_terms, d_tf, d_dl, avgdl, k1, b,
+                       method, d_idf, d_ip, d_ix, d_dt, d_dt64, d_err, st), "build_scores");
   int32_t herr = 0;
-  TRYB(hipMemcpyAsync(&herr, d_err, sizeof(int32_t), hipMemcpyDeviceToHost, st), "D2H err");
-  TRYB(hipStreamSynchronize(st), "build sync");
-  if (herr & 1) return cleanup(fail(BM25_EINVAL, "doc or term id out of range"));
-  if (herr & 2) return cleanup(fail(BM25_EINVAL, "term frequencies must be positive and finite"));
-  if (herr & 4) return cleanup(fail(BM25_EINVAL, "duplicate (doc, term) triple"));
-  TRYB(hipMemcpyAsync(out_indptr, d_ip, sizeof(int64_t) * (n_terms + 1), hipMemcpyDeviceToHost, st), "D2H indptr");
-  if (n_triples > 0) {
-    TRYB(hipMemcpyAsync(out_indices, d_ix, sizeof(int32_t) * n_triples, hipMemcpyDeviceToHost, st), "D2H indices");
-    TRYB(hipMemcpyAsync(out_data, d_dt, sizeof(float) * n_triples, hipMemcpyDeviceToHost, st), "D2H data");
-    if (out_data64)
-      TRYB(hipMemcpyAsync(out_data64, d_dt64, sizeof(double) * n_triples, hipMemcpyDeviceToHost, st), "D2H data64");
-  }
-  TRYB(hipStreamSynchronize(st), "build sync");
-#undef TRYB
-  return cleanup(BM25_OK);
+  c.download(&herr, d_err, 1, "D2H err");
+  if (c.ok()) c.run(hipStreamSynchronize(st), "build sync");
+  if (!c.ok()) herr = 0;  // (not read back)
+  if (herr & 1) c.hold(fail(BM25_EINVAL, "doc or term id out of range"));
+  else if (herr & 2) c.hold(fail(BM25_EINVAL, "term frequencies must be positive and finite"));
+  else if (herr & 4) c.hold(fail(BM25_EINVAL, "duplicate (doc, term) triple"));
+  c.download(out_indptr, d_ip, n_terms + 1, "D2H indptr");
+  c.download(out_indices, d_ix, n, "D2H indices");
+  c.download(out_data, d_dt, n, "D2H data");
+  if (out_data64) c.download(out_data64, d_dt64, n, "D2H data64");
+  return c.finish("build sync");
 }
 
 int bm25_scores_dense(bm25_index* h, const int32_t* query, int64_t T, float* out_scores) {
@@ -1501,30 +1373,18 @@ int bm25_scores_dense(bm25_index* h, const int32_t* query, int64_t T, float* out
   if (T < 0) return fail(BM25_EINVAL, "negative query length");
   if (!out_scores) return fail(BM25_EINVAL, "NULL output");
   if (T > 0 && !query) return fail(BM25_EINVAL, "NULL query");
-  int64_t mx = 0;
-  for (int64_t i = 0; i < T; ++i) mx = std::max<int64_t>(mx, query[i]);
-  if (mx >= h->ix.n_terms)
-    return fail(BM25_EINVAL,
-                "The maximum token ID in the query (%lld) is higher than the number of tokens in "
-                "the index.",
-                (long long)mx);
+  const int rc = check_token_ids(h->ix.n_terms, 0, query, T);
+  if (rc) return rc;
   if (h->ix.n_docs == 0) return BM25_OK;
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIP_TRY(hipSetDevice(h->ix.device), "hipSetDevice");
-  float* d_out = nullptr;
-  int32_t* d_qq = nullptr;
-  HIP_TRY(hipMalloc(&d_out, sizeof(float) * h->ix.n_docs), "hipMalloc(dense)");
-  hipError_t e = hipMalloc(&d_qq, sizeof(int32_t) * std::max<int64_t>(T, 1));
-  if (e == hipSuccess && T > 0)
-    e = hipMemcpyAsync(d_qq, query, sizeof(int32_t) * T, hipMemcpyHostToDevice, h->stream);
-  if (e == hipSuccess) e = launch_scores_dense(h->ix, d_qq, T, d_out, h->stream);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(out_scores, d_out, sizeof(float) * h->ix.n_docs, hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  hipFree(d_out);
-  hipFree(d_qq);
-  if (e != hipSuccess) return hip_fail(e, "scores_dense");
-  return BM25_OK;
+  Enter in(h);
+  if (in.rc) return in.rc;
+  HostCall c(h->stream);
+  float* d_out = c.alloc<float>(h->ix.n_docs, "hipMalloc(dense)");
+  int32_t* d_qq = c.alloc<int32_t>(T);
+  c.upload_to(d_qq, query, T);
+  if (c.ok()) c.run(launch_scores_dense(h->ix, d_qq, T, d_out, h->stream));
+  c.download(out_scores, d_out, h->ix.n_docs);
+  return c.finish("scores_dense");
 }
 
 int bm25_score_docs(bm25_index* h, const int32_t* queries, int64_t Q, int64_t T,
@@ -1535,43 +1395,26 @@ int bm25_score_docs(bm25_index* h, const int32_t* queries, int64_t Q, int64_t T,
   if (T > 0 && !queries) return fail(BM25_EINVAL, "NULL queries");
   if (!docs) return fail(BM25_EINVAL, "NULL docs");
   if (!out_scores) return fail(BM25_EINVAL, "NULL output");
-  // bm25_native.py:116-121: max(initial=0) >= n_terms -> ValueError
-  int64_t mx = 0;
-  for (int64_t i = 0; i < Q * T; ++i) mx = std::max<int64_t>(mx, queries[i]);
-  if (mx >= h->ix.n_terms)
-    return fail(BM25_EINVAL,
-                "The maximum token ID in the query (%lld) is higher than the number of tokens in "
-                "the index.",
-                (long long)mx);
+  const int rc = check_token_ids(h->ix.n_terms, 0, queries, Q * T);
+  if (rc) return rc;
   const int64_t lo = h->ix.doc_offset, hi = h->ix.doc_offset + h->ix.n_docs;
   for (int64_t i = 0; i < Q * C; ++i)
     if (docs[i] >= 0 && (docs[i] < lo || docs[i] >= hi))
       return fail(BM25_EINVAL, "doc id %lld (row %lld) is outside the index's documents [%lld, %lld)",
                   (long long)docs[i], (long long)(i / C), (long long)lo, (long long)hi);
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIP_TRY(hipSetDevice(h->ix.device), "hipSetDevice");
+  Enter in(h);
+  if (in.rc) return in.rc;
   // staging buffers of this call's own (as bm25_scores_dense): the search
   // workspace and the search staging buffers stay untouched
-  int32_t* d_qq = nullptr;
-  int32_t* d_dd = nullptr;
-  float* d_out = nullptr;
-  hipError_t e = hipMalloc(&d_qq, sizeof(int32_t) * std::max<int64_t>(Q * T, 1));
-  if (e == hipSuccess) e = hipMalloc(&d_dd, sizeof(int32_t) * Q * C);
-  if (e == hipSuccess) e = hipMalloc(&d_out, sizeof(float) * Q * C);
-  if (e == hipSuccess && Q * T > 0)
-    e = hipMemcpyAsync(d_qq, queries, sizeof(int32_t) * Q * T, hipMemcpyHostToDevice, h->stream);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(d_dd, docs, sizeof(int32_t) * Q * C, hipMemcpyHostToDevice, h->stream);
-  if (e == hipSuccess) e = launch_score_docs(h->ix, d_qq, Q, T, d_dd, C, d_out, h->stream);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(out_scores, d_out, sizeof(float) * Q * C, hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  else hipStreamSynchronize(h->stream);  // (copies in flight read the caller's arrays)
-  hipFree(d_qq);
-  hipFree(d_dd);
-  hipFree(d_out);
-  if (e != hipSuccess) return hip_fail(e, "score_docs");
-  return BM25_OK;
+  HostCall c(h->stream);
+  int32_t* d_qq = c.alloc<int32_t>(Q * T);
+  int32_t* d_dd = c.alloc<int32_t>(Q * C);
+  float* d_out = c.alloc<float>(Q * C);
+  c.upload_to(d_qq, queries, Q * T);
+  c.upload_to(d_dd, docs, Q * C);
+  if (c.ok()) c.run(launch_score_docs(h->ix, d_qq, Q, T, d_dd, C, d_out, h->stream));
+  c.download(out_scores, d_out, Q * C);
+  return c.finish("score_docs");
 }
 
 int bm25_score_docs_device(bm25_index* h, const int32_t* d_queries, int64_t Q, int64_t T,
@@ -1581,8 +1424,8 @@ int bm25_score_docs_device(bm25_index* h, const int32_t* d_queries, int64_t Q, i
   if (Q == 0 || C == 0) return BM25_OK;
   // reads the immutable index arrays only: no workspace, no ordering against
   // the handle's searches (ws_stream)
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIP_TRY(hipSetDevice(h->ix.device), "hipSetDevice");
+  Enter in(h);
+  if (in.rc) return in.rc;
   HIP_TRY(launch_score_docs(h->ix, d_queries, Q, T, d_docs, C, d_scores, (hipStream_t)stream),
           "score_docs launch");
   return BM25_OK;
@@ -1591,60 +1434,43 @@ int bm25_score_docs_device(bm25_index* h, const int32_t* d_queries, int64_t Q, i
 int bm25_index_set_values_f64(bm25_index* h, const double* data64) {
   if (!h || (h->ix.nnz > 0 && !data64)) return fail(BM25_EINVAL, "NULL argument");
   if (!h->arrays) return fail(BM25_EINVAL, "unbuilt index");
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIP_TRY(hipSetDevice(h->ix.device), "hipSetDevice");
+  Enter in(h);
+  if (in.rc) return in.rc;
   if (!h->ix.val64) {
     HIP_TRY(hipMalloc(&h->ix.val64, sizeof(double) * std::max<int64_t>(h->ix.nnz, 1)),
             "hipMalloc(val64)");
     h->arrays->p.push_back(h->ix.val64);  // freed with the index arrays
   }
-  if (h->ix.nnz > 0)
-    HIP_TRY(hipMemcpyAsync(h->ix.val64, data64, sizeof(double) * h->ix.nnz, hipMemcpyHostToDevice,
-                           h->stream), "H2D val64");
-  HIP_TRY(hipStreamSynchronize(h->stream), "val64 sync");
-  return BM25_OK;
+  HostCall c(h->stream);
+  c.upload_to(h->ix.val64, data64, h->ix.nnz, "H2D val64");
+  return c.finish("val64 sync");
 }
 
-// Device query + f64 dense sums of one query on h's stream (caller holds
-// h->mu and has set the device); *d_q / *d_out are freed by the caller.
-static int dense_f64_query(bm25_index* h, const int32_t* query, int64_t T, int32_t** d_q,
-                           double** d_out) {
-  if (T < 0) return fail(BM25_EINVAL, "negative query length");
-  if (T > 0 && !query) return fail(BM25_EINVAL, "NULL query");
-  if (!h->ix.val64) return fail(BM25_EINVAL, "no float64 values: bm25_index_set_values_f64 first");
-  int64_t mx = 0;
-  for (int64_t i = 0; i < T; ++i) mx = std::max<int64_t>(mx, query[i]);
-  if (mx >= h->ix.n_terms)
-    return fail(BM25_EINVAL,
-                "The maximum token ID in the query (%lld) is higher than the number of tokens in "
-                "the index.",
-                (long long)mx);
-  HIP_TRY(hipMalloc(d_q, sizeof(int32_t) * std::max<int64_t>(T, 1)), "hipMalloc(query)");
-  HIP_TRY(hipMalloc(d_out, sizeof(double) * std::max<int64_t>(h->ix.n_docs, 1)), "hipMalloc(dense)");
-  if (T > 0)
-    HIP_TRY(hipMemcpyAsync(*d_q, query, sizeof(int32_t) * T, hipMemcpyHostToDevice, h->stream),
-            "H2D query");
-  HIP_TRY(launch_dense_f64(h->ix, h->ix.val64, *d_q, T, *d_out, h->stream), "dense f64 launch");
-  return BM25_OK;
+// The f64 dense sums of one query, staged and enqueued through c (caller
+// holds h->mu and has set the device): the device row, owned by c.  A bad
+// query is c's held return code.
+static double* dense_f64_query(bm25_index* h, HostCall& c, const int32_t* query, int64_t T) {
+  if (T < 0) c.hold(fail(BM25_EINVAL, "negative query length"));
+  else if (T > 0 && !query) c.hold(fail(BM25_EINVAL, "NULL query"));
+  else if (!h->ix.val64)
+    c.hold(fail(BM25_EINVAL, "no float64 values: bm25_index_set_values_f64 first"));
+  else c.hold(check_token_ids(h->ix.n_terms, 0, query, T));
+  int32_t* d_q = c.alloc<int32_t>(T, "hipMalloc(query)");
+  double* d_out = c.alloc<double>(h->ix.n_docs, "hipMalloc(dense)");
+  c.upload_to(d_q, query, T, "H2D query");
+  if (c.ok())
+    c.run(launch_dense_f64(h->ix, h->ix.val64, d_q, T, d_out, h->stream), "dense f64 launch");
+  return d_out;
 }
 
 int bm25_scores_dense_f64(bm25_index* h, const int32_t* query, int64_t T, double* out_scores) {
   if (!h || !out_scores) return fail(BM25_EINVAL, "NULL argument");
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIP_TRY(hipSetDevice(h->ix.device), "hipSetDevice");
-  int32_t* d_q = nullptr;
-  double* d_out = nullptr;
-  int rc = dense_f64_query(h, query, T, &d_q, &d_out);
-  hipError_t e = hipSuccess;
-  if (rc == BM25_OK && h->ix.n_docs > 0)
-    e = hipMemcpyAsync(out_scores, d_out, sizeof(double) * h->ix.n_docs, hipMemcpyDeviceToHost,
-                       h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  hipFree(d_q);
-  hipFree(d_out);
-  if (rc) return rc;
-  if (e != hipSuccess) return hip_fail(e, "scores_dense_f64");
-  return BM25_OK;
+  Enter in(h);
+  if (in.rc) return in.rc;
+  HostCall c(h->stream);
+  const double* d_out = dense_f64_query(h, c, query, T);
+  c.download(out_scores, d_out, h->ix.n_docs);
+  return c.finish("scores_dense_f64");
 }
 
 int bm25_topn_f64(bm25_index* h, const int32_t* query, int64_t T, int64_t n, int32_t* out_docs,
@@ -1655,32 +1481,17 @@ int bm25_topn_f64(bm25_index* h, const int32_t* query, int64_t T, int64_t n, int
                 (long long)h->ix.n_docs);
   if (n > 0 && (!out_docs || !out_scores)) return fail(BM25_EINVAL, "NULL output");
   if (n == 0) return BM25_OK;
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIP_TRY(hipSetDevice(h->ix.device), "hipSetDevice");
-  int32_t* d_q = nullptr;
-  double* d_out = nullptr;
-  void* scratch = nullptr;
-  int32_t* d_docs = nullptr;
-  double* d_sc = nullptr;
-  int rc = dense_f64_query(h, query, T, &d_q, &d_out);
-  hipError_t e = hipSuccess;
-  if (rc == BM25_OK) {
-    e = hipMalloc(&scratch, topn_f64_scratch_bytes(h->ix.n_docs));
-    if (e == hipSuccess) e = hipMalloc(&d_docs, sizeof(int32_t) * n);
-    if (e == hipSuccess) e = hipMalloc(&d_sc, sizeof(double) * n);
-    if (e == hipSuccess)
-      e = launch_topn_f64(d_out, h->ix.n_docs, n, scratch, d_docs, d_sc, h->stream);
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(out_docs, d_docs, sizeof(int32_t) * n, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(out_scores, d_sc, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream);
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  else hipStreamSynchronize(h->stream);
-  for (void* p : {(void*)d_q, (void*)d_out, scratch, (void*)d_docs, (void*)d_sc}) hipFree(p);
-  if (rc) return rc;
-  if (e != hipSuccess) return hip_fail(e, "topn_f64");
-  return BM25_OK;
+  Enter in(h);
+  if (in.rc) return in.rc;
+  HostCall c(h->stream);
+  const double* d_out = dense_f64_query(h, c, query, T);
+  void* scratch = c.alloc<char>((int64_t)topn_f64_scratch_bytes(h->ix.n_docs));
+  int32_t* d_docs = c.alloc<int32_t>(n);
+  double* d_sc = c.alloc<double>(n);
+  if (c.ok()) c.run(launch_topn_f64(d_out, h->ix.n_docs, n, scratch, d_docs, d_sc, h->stream));
+  c.download(out_docs, d_docs, n);
+  c.download(out_scores, d_sc, n);
+  return c.finish("topn_f64");
 }
 
 int bm25_merge_topk_device(int device, const int32_t* d_docs, const float* d_scores, int64_t W,
@@ -1739,8 +1550,8 @@ int bm25_search_stats(bm25_index* h, int64_t* rescored_tiles, int64_t* fallback_
 int bm25_search_stats_ex(bm25_index* h, int64_t* rescored_tiles, int64_t* fallback_queries,
                          int64_t* bound_skipped) {
   if (!h) return fail(BM25_EINVAL, "NULL index");
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIP_TRY(hipSetDevice(h->ix.device), "hipSetDevice");
+  Enter in(h);
+  if (in.rc) return in.rc;
   int32_t cnt[kCounters] = {};
   read_counters(h, cnt);
   if (rescored_tiles) *rescored_tiles = cnt[3];
@@ -1752,8 +1563,8 @@ int bm25_search_stats_ex(bm25_index* h, int64_t* rescored_tiles, int64_t* fallba
 int bm25_search_counters(bm25_index* h, int64_t* out, int32_t n) {
   if (!h || !out) return fail(BM25_EINVAL, "NULL argument");
   if (n < 1 || n > 6) return fail(BM25_EINVAL, "n=%d must be in 1..6", n);
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIP_TRY(hipSetDevice(h->ix.device), "hipSetDevice");
+  Enter in(h);
+  if (in.rc) return in.rc;
   int32_t cnt[kCounters] = {};
   read_counters(h, cnt);
   uint64_t post = 0;
@@ -1862,6 +1673,18 @@ int sharded_free(bm25_sharded* s) {
   return BM25_OK;
 }
 
+// Waits for every shard's stream when a sharded search fails part-way (s =
+// nullptr: it ended, drained).
+struct DrainShards {
+  bm25_sharded* s;
+  ~DrainShards() {
+    for (size_t r = 0; s && r < s->shards.size(); ++r) {
+      hipSetDevice(s->shards[r]->ix.device);
+      hipStreamSynchronize(s->shards[r]->stream);
+    }
+  }
+};
+
 }  // namespace
 
 extern "C" {
@@ -1957,13 +1780,8 @@ int bm25_sharded_search(bm25_sharded* s, const int32_t* queries, int64_t Q, int6
   if (Q == 0 || k == 0) return BM25_OK;
   if (T > 0 && !queries) return fail(BM25_EINVAL, "NULL queries");
   if (!out_docs || !out_scores) return fail(BM25_EINVAL, "NULL output");
-  int64_t mx = 0;
-  for (int64_t i = 0; i < Q * T; ++i) mx = std::max<int64_t>(mx, queries[i]);
-  if (mx >= s->n_terms)
-    return fail(BM25_EINVAL,
-                "The maximum token ID in the query (%lld) is higher than the number of tokens in "
-                "the index.",
-                (long long)mx);
+  int rc = check_token_ids(s->n_terms, 0, queries, Q * T);
+  if (rc) return rc;
   const int64_t W = (int64_t)s->shards.size();
   std::lock_guard<std::mutex> lk(s->mu);
   bm25_index* h0 = s->shards[0];
@@ -1974,6 +1792,7 @@ int bm25_sharded_search(bm25_sharded* s, const int32_t* queries, int64_t Q, int6
     hipFree(s->g_scores);
     s->g_docs = nullptr;
     s->g_scores = nullptr;
+    s->cap_g = 0;
     HIP_TRY(hipMalloc(&s->g_docs, sizeof(int32_t) * W * out), "hipMalloc(shard lists)");
     HIP_TRY(hipMalloc(&s->g_scores, sizeof(float) * W * out), "hipMalloc(shard lists)");
     s->cap_g = W * out;
@@ -1983,15 +1802,17 @@ int bm25_sharded_search(bm25_sharded* s, const int32_t* queries, int64_t Q, int6
     hipFree(s->m_scores);
     s->m_docs = nullptr;
     s->m_scores = nullptr;
+    s->cap_m = 0;
     HIP_TRY(hipMalloc(&s->m_docs, sizeof(int32_t) * out), "hipMalloc(merged)");
     HIP_TRY(hipMalloc(&s->m_scores, sizeof(float) * out), "hipMalloc(merged)");
     s->cap_m = out;
   }
   // sample width: the same on every shard (bm25_sample_width's rule)
   int64_t S = 0;
-  int rc = bm25_sample_width(h0, s->shard_docs_max, (int32_t)W, k, &S);
+  rc = bm25_sample_width(h0, s->shard_docs_max, (int32_t)W, k, &S);
   if (rc) return rc;
   if (Q * S > s->cap_keys) {
+    s->cap_keys = 0;
     for (int64_t r = 0; r < W; ++r) {
       HIP_TRY(hipSetDevice(s->shards[r]->ix.device), "hipSetDevice");
       hipStreamSynchronize(s->shards[r]->stream);
@@ -2003,6 +1824,9 @@ int bm25_sharded_search(bm25_sharded* s, const int32_t* queries, int64_t Q, int6
     }
     s->cap_keys = Q * S;
   }
+  // from here on the shards' streams read and write the caller's arrays:
+  // no return before they have drained
+  DrainShards drain{s};
   // 1. every shard: H2D queries + its sample keys, on its own stream
   for (int64_t r = 0; r < W; ++r) {
     bm25_index* h = s->shards[r];
@@ -2071,6 +1895,7 @@ int bm25_sharded_search(bm25_sharded* s, const int32_t* queries, int64_t Q, int6
     HIP_TRY(hipSetDevice(s->shards[r]->ix.device), "hipSetDevice");
     HIP_TRY(hipEventSynchronize(s->keyed[r]), "hipEventSynchronize");
   }
+  drain.s = nullptr;  // (they have)
   return BM25_OK;
 }
 

@@ -1,0 +1,140 @@
+// bm25mi_host.h — host-only helpers of the C-ABI boundary (bm25mi_capi.cpp;
+// tests/asan/host_check.cpp drives them without a device): the error
+// reporters, the staging helper of the synchronous host-pointer calls and the
+// table of the search options.  No .hip file includes this.
+//
+// A host entry point reads: validate, Enter (bm25mi_capi.cpp), HostCall,
+// finish.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <vector>
+
+#include "../../include/bm25mi.h"
+#include "bm25mi_internal.h"
+
+namespace bm25mi {
+
+// Set bm25_last_error of the calling thread and return the code.
+int fail(int code, const char* fmt, ...);
+int hip_fail(hipError_t e, const char* what);  // "<what>: <HIP's text> (<name>)": EHIP or ENOMEM
+
+// One synchronous host-pointer call on one stream.  It owns the device
+// buffers it allocates, holds the first failure — a hipError_t, or the
+// return code of a device pipeline (run_search), which wins — and turns every
+// step after it into a no-op, so a call body reads top to bottom; guard a
+// launch that takes the buffers with ok().  finish() always waits for the
+// stream before a buffer is freed and before the caller gets its arrays
+// back: copies in flight read and write them.
+class HostCall {
+ public:
+  explicit HostCall(hipStream_t st) : st_(st) {}
+  HostCall(const HostCall&) = delete;
+  HostCall& operator=(const HostCall&) = delete;
+  ~HostCall() {
+    if (!finished_) hipStreamSynchronize(st_);
+    for (void* p : bufs_) hipFree(p);
+  }
+
+  bool ok() const { return rc_ == BM25_OK && err_ == hipSuccess; }
+  // Holds e if it is the first failure (what: its label in the error text,
+  // finish's by default).
+  void run(hipError_t e, const char* what = nullptr) {
+    if (ok() && e != hipSuccess) {
+      err_ = e;
+      what_ = what;
+    }
+  }
+  // Holds a failed call's return code (its message is already set).
+  void hold(int rc) {
+    if (rc_ == BM25_OK) rc_ = rc;
+  }
+  template <class T>
+  T* alloc(int64_t n, const char* what = nullptr) {
+    void* p = nullptr;
+    if (ok()) run(hipMalloc(&p, sizeof(T) * (size_t)std::max<int64_t>(n, 1)), what);
+    if (p) bufs_.push_back(p);
+    return (T*)p;
+  }
+  // Host to device, into a buffer of the caller's (n <= 0: nothing).
+  template <class T>
+  void upload_to(T* dst, const T* src, int64_t n, const char* what = nullptr) {
+    if (ok() && n > 0)
+      run(hipMemcpyAsync(dst, src, sizeof(T) * (size_t)n, hipMemcpyHostToDevice, st_), what);
+  }
+  // A device copy of src[0..n) (null for n <= 0).
+  template <class T>
+  T* upload(const T* src, int64_t n, const char* what = nullptr) {
+    if (n <= 0) return nullptr;
+    T* d = alloc<T>(n, what);
+    upload_to(d, src, n, what);
+    return d;
+  }
+  template <class T>
+  void download(T* dst, const T* src, int64_t n, const char* what = nullptr) {
+    if (ok() && n > 0)
+      run(hipMemcpyAsync(dst, src, sizeof(T) * (size_t)n, hipMemcpyDeviceToHost, st_), what);
+  }
+  int finish(const char* what) {
+    const hipError_t es = hipStreamSynchronize(st_);
+    finished_ = true;
+    if (rc_) return rc_;
+    run(es);
+    return err_ == hipSuccess ? BM25_OK : hip_fail(err_, what_ ? what_ : what);
+  }
+
+ private:
+  hipStream_t st_;
+  std::vector<void*> bufs_;
+  hipError_t err_ = hipSuccess;
+  const char* what_ = nullptr;
+  int rc_ = BM25_OK;
+  bool finished_ = false;
+};
+
+// The search options (SearchOpts; include/bm25mi.h describes them): name, the
+// variable a new handle reads, the field, and the values set_opt accepts — a
+// bool, lo..hi, or a power of two in lo..hi (lo = 0: 0 too).  msg: the error
+// text where it does not follow from those.  The environment is looser than
+// set_opt, as it always was: a bool is value != 0, env_clamp bounds an
+// integer from below (1) or on both sides (2), the others are taken as given.
+enum OptKind { kOptBool, kOptRange, kOptPow2 };
+struct OptDesc {
+  const char* name;
+  const char* env;
+  int SearchOpts::*field;
+  OptKind kind;
+  int lo, hi;
+  int env_clamp;
+  const char* msg;
+};
+inline constexpr OptDesc kOpts[] = {
+    {"flat", "BM25_FLAT", &SearchOpts::flat, kOptBool, 0, 1, 0, nullptr},
+    {"flat_bw", "BM25_FLAT_BW", &SearchOpts::flat_bw, kOptPow2, 0, 8, 0,
+     "flat_bw must be 0, 1, 2, 4 or 8"},
+    {"items_per_wave", "BM25_ITEMS_PER_WAVE", &SearchOpts::items_per_wave, kOptRange, 1, 1024, 0,
+     nullptr},
+    {"sample_p", "BM25_SAMPLE_P", &SearchOpts::sample_p, kOptPow2, 1, 64, 0, nullptr},
+    {"list_cap", "BM25_LIST_CAP", &SearchOpts::list_cap, kOptRange, 0, 1 << 20, 0,
+     "list_cap must be in 0..2^20"},
+    {"claim_ch", "BM25_CLAIM_CH", &SearchOpts::claim_ch, kOptRange, 1, 64, 0, nullptr},
+    {"claim_m", "BM25_CLAIM_M", &SearchOpts::claim_m, kOptRange, 1, kClaimM, 0, nullptr},
+    {"tile_bound", "BM25_TILE_BOUND", &SearchOpts::tile_bound, kOptBool, 0, 1, 0, nullptr},
+    {"theta_bound", "BM25_THETA_BOUND", &SearchOpts::theta_bound, kOptBool, 0, 1, 0, nullptr},
+    {"grid_pct", "BM25_GRID_PCT", &SearchOpts::grid_pct, kOptRange, 1, 100, 2, nullptr},
+    {"count_skips", "BM25_COUNT_SKIPS", &SearchOpts::count_skips, kOptBool, 0, 1, 0, nullptr},
+    {"large_lists", "BM25_LARGE_LISTS", &SearchOpts::large_lists, kOptBool, 0, 1, 0, nullptr},
+    {"rest_split", "BM25_REST_SPLIT", &SearchOpts::rest_split, kOptBool, 0, 1, 0, nullptr},
+    {"bound_pool", "BM25_BOUND_POOL", &SearchOpts::bound_pool, kOptBool, 0, 1, 0, nullptr},
+    {"filter_tiles", "BM25_FILTER_TILES", &SearchOpts::filter_tiles, kOptBool, 0, 1, 0, nullptr},
+    {"bool_chunk", "BM25_BOOL_CHUNK", &SearchOpts::bool_chunk, kOptRange, 0, 1 << 30, 1,
+     "bool_chunk must be in 0..2^30"},
+};
+
+// Sets / reads one option by name (EINVAL names the accepted values).
+int set_opt(SearchOpts& o, const char* name, int64_t v);
+int get_opt(const SearchOpts& o, const char* name, int64_t* v);
+
+}  // namespace bm25mi

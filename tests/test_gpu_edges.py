@@ -512,3 +512,130 @@ def test_max_token_device_sizes(gpu):
         assert index.max_token_device(torch.from_numpy(base).cuda().view(shape)) == \
             int(base.max(initial=0)), n
     index.close()
+
+
+# ------------------------------------------- the host calls' shared staging
+def test_host_calls_reject_token_ids_and_stay_usable(gpu):
+    """Every synchronous host-pointer call goes through one staging helper
+    (csrc/bm25mi_host.h).  On the 5-document, 3-term index of
+    tests/asan/host_check.cpp: a token id of 3 (= n_terms) gives EINVAL with
+    the reference's message from each call that takes token ids, a term id or
+    a CSC the device rejects gives EINVAL from bm25_build_scores and
+    bm25_index_create, and after each failure the same call with valid
+    arguments is bit-exact against the CPU reference — the handle is left
+    usable.  Then all 16 search options round-trip through
+    bm25_index_set_option / bm25_index_get_option, and the search still
+    matches."""
+    from bm25mi.scoring import build_scores
+    N, V = 5, 3
+    ip = np.array([0, 2, 2, 5], np.int64)
+    ix = np.array([0, 3, 1, 2, 4], np.int32)
+    dt = np.array([1.0, 2.0, 0.5, 0.25, 3.0], np.float32)
+    d64 = dt.astype(np.float64) + 1e-9
+    index = _idx(ip, ix, dt, N)
+    index.set_values_f64(d64)
+    msg = (r"The maximum token ID in the query \(3\) is higher than the number of tokens in "
+           r"the index\.")
+    good = np.array([[0, 2], [2, -1], [1, 1]], np.int32)
+    bad = good.copy()
+    bad[1, 1] = V
+    dense = np.stack([oracle.scores_dense_c(N, ip, ix, dt, r) for r in good])
+    holds = np.zeros((V, N), bool)           # holds[t, d]: document d has term t
+    for t in range(V):
+        holds[t, ix[ip[t]:ip[t + 1]]] = True
+
+    def pack(allow):                          # bool [M, N] -> uint32 [M, 1]
+        return (allow.astype(np.uint32) << np.arange(N, dtype=np.uint32)).sum(1, keepdims=True) \
+            .astype(np.uint32)
+
+    def filtered_ref(allow, k):               # top-k among the allowed, padded
+        rd = np.full((len(good), k), -1, np.int32)
+        rs = np.full((len(good), k), np.uint32(0xFFFFFFFF).view(np.float32), np.float32)
+        for i, row in enumerate(dense):
+            docs = np.nonzero(allow[i])[0]
+            order = docs[np.lexsort((docs, -row[docs].astype(np.float64)))][:k]
+            rd[i, :len(order)], rs[i, :len(order)] = order, row[order]
+        return rd, rs
+
+    k = 3
+    allow = np.array([[1, 1, 0, 1, 1], [0, 0, 1, 0, 1], [1, 0, 0, 0, 0]], bool)
+    must, must_bad = [[0], [2], []], [[0], [V], []]
+    not_, any_ = [[], [0], [2]], [[2, 0], [], [0, 1]]
+    built = np.stack([(holds[0] | holds[2]) & holds[0],
+                      holds[2] & ~holds[0],
+                      (holds[0] | holds[1]) & ~holds[2]])
+    assert built.any(1).all() and not built.all(1).any()
+    cand = np.array([[0, 4, -1], [3, 3, 1], [2, 0, 4]], np.int32)
+    cand_ref = np.where(cand >= 0, np.take_along_axis(dense, np.maximum(cand, 0), 1), 0) \
+        .astype(np.float32)
+
+    def same64(got, want):
+        assert np.array_equal(got.view(np.uint64), want.view(np.uint64)), (got, want)
+
+    f64_ref = oracle.scores_f64(N, ip, ix, d64, [0, 2])
+    calls = [  # (the call with token ids `q` / clause `m`, the check of its valid result)
+        (lambda q, m: index.search(q, k),
+         lambda r: _exact(r, oracle.search_c(N, ip, ix, dt, good, k))),
+        (lambda q, m: index.search_filtered(q, k, allow, np.arange(3, dtype=np.int32)),
+         lambda r: _exact(r, filtered_ref(allow, k))),
+        (lambda q, m: index.term_masks(must=m, any=any_, must_not=not_),
+         lambda r: np.testing.assert_array_equal(r, pack(built))),
+        (lambda q, m: index.search_boolean(q, k, must=must, any=any_, must_not=not_),
+         lambda r: _exact(r, filtered_ref(built, k))),
+        (lambda q, m: index.search_boolean(good, k, must=m, any=any_, must_not=not_),
+         lambda r: _exact(r, filtered_ref(built, k))),
+        (lambda q, m: index.scores_dense(q[1]),
+         lambda r: np.testing.assert_array_equal(r.view(np.uint32), dense[1].view(np.uint32))),
+        (lambda q, m: index.score_docs(q, cand),
+         lambda r: np.testing.assert_array_equal(r.view(np.uint32), cand_ref.view(np.uint32))),
+        (lambda q, m: index.scores_dense_f64(q[0] if q is good else q[1]),
+         lambda r: same64(r, f64_ref)),
+        (lambda q, m: index.topn_f64(q[0] if q is good else q[1], 4),
+         lambda r: (np.testing.assert_array_equal(r[0], oracle.topn_f64(f64_ref, 4)[0]),
+                    same64(r[1], oracle.topn_f64(f64_ref, 4)[1]))),
+    ]
+    for i, (call, check) in enumerate(calls):
+        with pytest.raises(ValueError, match=msg):
+            call(bad, must_bad)
+        check(call(good, must))
+        _exact(index.search(good, k), oracle.search_c(N, ip, ix, dt, good, k))
+
+    # the two calls without a handle: the device's own checks, mid-call
+    docs, terms = np.array([0, 1, 1], np.int32), np.array([0, 0, 2], np.int32)
+    tfs, dl = np.array([1.0, 2.0, 1.0], np.float32), np.array([3, 4], np.int32)
+    with pytest.raises(ValueError, match="doc or term id out of range"):
+        build_scores(docs, np.array([0, 0, V], np.int32), tfs, dl, V)
+    ref = oracle.build_scores_numpy(docs, terms, tfs, dl, V, 1.5, 0.75, "lucene", 3.5,
+                                    idf=oracle.idf_numpy(np.bincount(terms, minlength=V), 2))
+    got = build_scores(docs, terms, tfs, dl, V, k1=1.5, b=0.75, method="lucene", avgdl=3.5,
+                       idf=oracle.idf_numpy(np.bincount(terms, minlength=V), 2))
+    assert np.array_equal(got[0], ref[0]) and np.array_equal(got[1], ref[1])
+    assert np.array_equal(got[2].view(np.uint32), ref[2].view(np.uint32))
+    with pytest.raises(ValueError, match="indices must be sorted, unique"):
+        _idx(ip, np.array([3, 0, 1, 2, 4], np.int32), dt, N)
+    for segments in ("dense", "sparse"):
+        again = _idx(ip, ix, dt, N, segments=segments)
+        _exact(again.search(good, k), oracle.search_c(N, ip, ix, dt, good, k))
+        again.close()
+
+    # all 16 options through the C-ABI: default, an accepted value, back
+    options = {"flat": (1, 0), "flat_bw": (0, 4), "items_per_wave": (4, 9), "sample_p": (8, 2),
+               "list_cap": (0, 4096), "claim_ch": (1, 3), "claim_m": (4, 8), "tile_bound": (1, 0),
+               "theta_bound": (1, 0), "grid_pct": (100, 50), "count_skips": (0, 1),
+               "large_lists": (1, 0), "rest_split": (0, 1), "bound_pool": (1, 0),
+               "filter_tiles": (1, 0), "bool_chunk": (0, 2)}
+    assert len(options) == 16
+    fresh = _idx(ip, ix, dt, N)
+    for name, (default, value) in options.items():
+        assert fresh.get_option(name) == default, name
+        fresh.set_option(name, value)
+        assert fresh.get_option(name) == value, name
+    with pytest.raises(ValueError, match="^unknown option 'x'$"):
+        fresh.set_option("x", 1)
+    with pytest.raises(ValueError, match="^grid_pct must be in 1..100$"):
+        fresh.set_option("grid_pct", 0)
+    _exact(fresh.search(good, k), oracle.search_c(N, ip, ix, dt, good, k))
+    _exact(fresh.search_boolean(good, k, must=must, any=any_, must_not=not_),
+           filtered_ref(built, k))
+    fresh.close()
+    index.close()
