@@ -298,6 +298,83 @@ int bm25_search_filtered_device(bm25_index* idx, const int32_t* d_queries, int64
 int bm25_search_filtered_stats(bm25_index* idx, int64_t* out, int32_t n);
 
 /*
+ * Weighted query terms: term boosts ("rust^2 gpu^0.5"), query expansion at
+ * fractional weight, learned sparse queries (uniCOIL, SPLADE, DeepImpact: the
+ * document impacts are the index values, the query is a weighted vector) and
+ * negative feedback.
+ * Replaces no reference call: BM25v.search takes no weights
+ * (bm25_native.py:76-158).
+ *   queries    [Q, T] int32 as in bm25_search (negative = padding)
+ *   weights    [Q, T] f32, weights[q][j] belongs to queries[q][j]
+ * The score of handle-local document d under query row q is the fold
+ *     acc = +0.0f
+ *     for j = 0 .. T-1, in query order:
+ *       if queries[q][j] is a valid id and the index stores a posting
+ *       (queries[q][j], d) with value v:
+ *         p   = weights[q][j] * v    rounded to fp32 on its own
+ *         acc = acc + p              a separate fp32 add: never an FMA
+ *     score(q, d) = acc
+ * A repeated id is added each time it occurs, each time with its own weight.
+ * The weight of a padding slot (a negative id; in the device calls also an id
+ * >= n_terms) is never read into a score and may hold anything, NaN included.
+ * Two identities follow from the fold:
+ *   - a weight of exactly 1.0f gives p == v, so a row of all-1.0f weights has
+ *     the bits of bm25_search_filtered — and of bm25_search, bm25_scores_dense
+ *     and bm25_score_docs;
+ *   - a weight of +0.0f or -0.0f leaves acc as it is (acc starts at +0.0f and
+ *     never becomes -0.0f), so weight 0.0f is bit for bit the same as padding.
+ * Weights must be finite.  The host calls reject a non-finite weight on a
+ * non-padding slot with BM25_EINVAL (the message names row, column and
+ * value).  The device calls validate nothing: a row with a non-finite weight
+ * has unspecified contents, the other rows are unaffected and nothing outside
+ * the caller's buffers is read or written.
+ * Documents no valid term touches are candidates at +0.0f, as everywhere
+ * else; with negative weights zero-score documents outrank negative ones.
+ * Order: score descending, then doc id ascending; padding is doc -1 / score
+ * bits 0xFFFFFFFF.
+ *
+ *   bm25_search_weighted(_device): bm25_search_filtered(_device) with the fold
+ *     above in place of the plain sum.  masks [M, W], query_mask [Q] (-1 = no
+ *     filter), padding rows, 0 <= k <= n_docs, the filter_tiles and list_cap
+ *     options, the one possible stream synchronisation, the retained scratch
+ *     and bm25_search_filtered_stats are as documented there.  One
+ *     difference: with M == 0 a NULL query_mask means "no filter for every
+ *     query" (the common case needs no array of -1); with M >= 1 NULL still
+ *     means mask 0.  The search always takes the filtered search's exact
+ *     passes; the tile-bound threshold of bm25_search is not used: weight *
+ *     bound is no upper bound of weight * value when the weight is negative,
+ *     and those passes need no bound (their threshold is a candidate's own
+ *     key), so they are exact for weights and values of either sign.
+ *     bm25_search_dispatch reports the flag 8192 after a weighted search.
+ *     Host call: validates as bm25_search_filtered, plus the finite-weight
+ *     rule.  Device call: shapes and NULL pointers only; token ids >= n_terms
+ *     are padding.
+ *   bm25_score_docs_weighted(_device): bm25_score_docs(_device) under the same
+ *     fold: out[q][c] is bit for bit the score bm25_search_weighted reports
+ *     for docs[q][c].  A posting that is absent adds +0.0f (not weight * 0).
+ *     The device call keeps the properties of bm25_score_docs_device: it reads
+ *     the index arrays only, is not ordered against the handle's searches,
+ *     never synchronises, and doc ids outside the handle's range score +0.0f,
+ *     so doc shards' outputs add up element-wise.  Host call: validates as
+ *     bm25_score_docs, plus the finite-weight rule.
+ * Subnormal products follow the device's fp32 denormal mode.
+ */
+int bm25_search_weighted(bm25_index* idx, const int32_t* queries, const float* weights, int64_t Q,
+                         int64_t T, int32_t k, const uint32_t* masks, int64_t M,
+                         const int32_t* query_mask, int32_t* out_docs, float* out_scores);
+int bm25_search_weighted_device(bm25_index* idx, const int32_t* d_queries, const float* d_weights,
+                                int64_t Q, int64_t T, int32_t k, const uint32_t* d_masks,
+                                int64_t M, const int32_t* d_query_mask, int32_t* d_docs,
+                                float* d_scores, void* stream);
+int bm25_score_docs_weighted(bm25_index* idx, const int32_t* queries, const float* weights,
+                             int64_t Q, int64_t T, const int32_t* docs, int64_t C,
+                             float* out_scores);
+int bm25_score_docs_weighted_device(bm25_index* idx, const int32_t* d_queries,
+                                    const float* d_weights, int64_t Q, int64_t T,
+                                    const int32_t* d_docs, int64_t C, float* d_scores,
+                                    void* stream);
+
+/*
  * Boolean term filters: the allow-masks of "+rust -java" — must contain all
  * of these terms, at least one of those, none of these — built on the device
  * from the index's own postings, in exactly the layout
@@ -654,7 +731,9 @@ int bm25_index_get_option(const bm25_index* idx, const char* name, int64_t* valu
  *                flag): REST counted its skipped postings (count_skips);
  *                1024 (a flag): REST ran over split items (rest_split);
  *                2048 (a flag): the threshold read the pooled bounds (bound_pool);
- *                4096: the filtered search's tile passes (its dense path sets 64)
+ *                4096: the filtered search's tile passes (its dense path sets 64);
+ *                8192 (a flag): the last search was weighted
+ *                (bm25_search_weighted; it sets 4096 and / or 64 as well)
  *   *term_lanes  flat kernel: term lanes per tile (8, 16, 32 or 64)
  *   band_tiles   [3]: flat kernel tiles per item of ALL, SAMPLE, REST
  *   *sample_p    sampling stride of the search (1: exact pass, 0: tile-bound

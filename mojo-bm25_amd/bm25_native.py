@@ -157,6 +157,36 @@ class BM25v:
         return self._gpu.search_filtered(queries, top_k, allow,
                                          np.arange(queries.shape[0], dtype=np.int32))
 
+    def search_weighted(self, queries, weights, top_k: int) -> Tuple[np.ndarray, np.ndarray]:
+        """search with a weight per query term (not in the reference, whose
+        search takes no weights): term boosts, expansion terms at fractional
+        weight, learned sparse queries, negative feedback.  ``weights`` is a
+        float [Q, T] array beside ``queries``; a document's score is the fp32
+        sum, in query order, of float32(weight * value) over the terms it
+        holds.  Weights of 1.0 give search's result bit for bit; the weight of
+        a padding slot is ignored, the others must be finite.  Returns
+        search's tuple: doc ids (int32) and scores (f32), [Q, top_k]."""
+        if len(queries) == 0:
+            return np.zeros((0, 0), dtype=self.dtype), np.zeros((0, 0), dtype=self.dtype)
+        if (not isinstance(queries, np.ndarray) or queries.ndim != 2
+                or not isinstance(queries[0][0], TokId)):
+            raise ValueError("The queries must be a list of list of query token IDs.")
+        weights = np.asarray(weights)
+        if weights.ndim != 2 or weights.shape != queries.shape:
+            raise ValueError(f"weights must be a float array of the queries' shape "
+                             f"{queries.shape}, got shape {weights.shape}")
+        if top_k < 0:
+            raise ValueError("negative dimensions are not allowed")
+        max_token_id = int(queries.max(initial=0))
+        n_terms = self._gpu.n_terms if self._gpu is not None else len(self.doc_toks.indptr) - 1
+        if max_token_id >= n_terms:
+            raise ValueError(
+                f"The maximum token ID in the query ({max_token_id}) is higher than the number "
+                "of tokens in the index.")
+        if self._gpu is None:
+            raise ValueError("BM25v index not built. Call index() first.")
+        return self._gpu.search_weighted(queries, weights, top_k)
+
     def search_boolean(self, queries, top_k: int, must=None, any=None, must_not=None,
                        base=None) -> Tuple[np.ndarray, np.ndarray]:
         """search under boolean term filters (not in the reference, whose

@@ -64,6 +64,12 @@ _SIGS = {
     "bm25_search_filtered_device": ([_P, _P, _I64, _I64, _I32, _P, _I64, _P, _P, _P, _P],
                                     ctypes.c_int),
     "bm25_search_filtered_stats": ([_P, _PI64, _I32], ctypes.c_int),
+    "bm25_search_weighted": ([_P, _P, _P, _I64, _I64, _I32, _P, _I64, _P, _P, _P], ctypes.c_int),
+    "bm25_search_weighted_device": ([_P, _P, _P, _I64, _I64, _I32, _P, _I64, _P, _P, _P, _P],
+                                    ctypes.c_int),
+    "bm25_score_docs_weighted": ([_P, _P, _P, _I64, _I64, _P, _I64, _P], ctypes.c_int),
+    "bm25_score_docs_weighted_device": ([_P, _P, _P, _I64, _I64, _P, _I64, _P, _P],
+                                        ctypes.c_int),
     "bm25_term_masks": ([_P, _P, _I64, _P, _I64, _P, _I64, _I64, _P, _I64, _P], ctypes.c_int),
     "bm25_term_masks_device": ([_P, _P, _I64, _P, _I64, _P, _I64, _I64, _P, _I64, _P, _P],
                                ctypes.c_int),

@@ -24,7 +24,7 @@ from __future__ import annotations
 import json
 import os
 from dataclasses import dataclass
-from typing import Dict, Iterable, List, Optional
+from typing import Dict, Iterable, List, Optional, Tuple
 
 import numpy as np
 
@@ -150,3 +150,23 @@ def query_ids(queries: Iterable[Iterable[str]], vocab: Dict[str, int], n_terms: 
         r = r[:w]
         out[i, :len(r)] = r
     return out
+
+
+def weighted_query_ids(queries: Iterable[Iterable[Tuple[str, float]]], vocab: Dict[str, int],
+                       n_terms: int, width: Optional[int] = None
+                       ) -> Tuple[np.ndarray, np.ndarray]:
+    """(token, weight) lists -> (int32 [Q, width] ids, float32 [Q, width]
+    weights) for search_weighted: query_ids' drop rules (a token absent from
+    the vocabulary or without a CSC column goes, with its weight), ids padded
+    with -1 and weights with 0.0.  The kept pairs stay in their order — the
+    order is the rounding order of the fp32 sum."""
+    rows = [[(vocab[t], float(x)) for t, x in q if t in vocab and vocab[t] < n_terms]
+            for q in queries]
+    w = width if width is not None else max([len(r) for r in rows] + [1])
+    ids = np.full((len(rows), w), -1, np.int32)
+    wts = np.zeros((len(rows), w), np.float32)
+    for i, r in enumerate(rows):
+        r = r[:w]
+        ids[i, :len(r)] = [t for t, _ in r]
+        wts[i, :len(r)] = [x for _, x in r]
+    return ids, wts

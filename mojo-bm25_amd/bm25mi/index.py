@@ -413,6 +413,125 @@ class GpuIndex:
         check(lib.bm25_search_filtered_stats(self._h, v, 3))
         return int(v[0]), int(v[1]), int(v[2])
 
+    # ------------------------------------------------- weighted query terms
+    @staticmethod
+    def _weights_arg(q: np.ndarray, weights) -> np.ndarray:
+        """weights -> float32 of the queries' [Q, T] shape (shape errors raised
+        here, before any C call)."""
+        w = np.ascontiguousarray(weights, dtype=np.float32)
+        if w.ndim != 2 or w.shape != q.shape:
+            raise ValueError(f"weights must be a float32 array of the queries' shape {q.shape}, "
+                             f"got shape {w.shape}")
+        return w
+
+    def search_weighted(self, queries: np.ndarray, weights, k: int, masks=None,
+                        query_mask=None) -> Tuple[np.ndarray, np.ndarray]:
+        """Top-k under weighted query terms (bm25_search_weighted, host
+        arrays): queries int32 [Q, T], weights float32 [Q, T], one weight per
+        slot.  A document's score is the fp32 sum, in query order from +0.0, of
+        float32(weight * value) over the terms it holds — 1.0 everywhere is
+        search / search_filtered bit for bit, a weight of 0.0 is the same as
+        padding; the weight of a padding slot is ignored, every other must be
+        finite.  masks / query_mask as in search_filtered; masks None: no
+        filter (query_mask must then be None or all -1)."""
+        q = np.ascontiguousarray(queries, dtype=np.int32)
+        if q.ndim != 2:
+            raise ValueError("queries must be a 2-D [Q, T] int32 array")
+        Q, T = q.shape
+        w = self._weights_arg(q, weights)
+        m = None if masks is None else self._masks_arg(masks)
+        M = 0 if m is None else m.shape[0]
+        qm = None
+        if query_mask is not None:
+            qm = np.ascontiguousarray(query_mask, dtype=np.int32)
+            if qm.ndim != 1 or qm.size != Q:
+                raise ValueError(f"query_mask must hold one mask id per query ({Q}), "
+                                 f"got shape {qm.shape}")
+            if qm.size and (int(qm.min()) < -1 or int(qm.max()) >= M):
+                raise ValueError(f"query_mask entries must be in [-1, {M})")
+        k = int(k)
+        docs = np.zeros((Q, max(k, 0)), np.int32)
+        scores = np.zeros((Q, max(k, 0)), np.float32)
+        check(lib.bm25_search_weighted(self._h, _ptr(q), _ptr(w), Q, T, k, _ptr(m) if M else None,
+                                       M, _ptr(qm), _ptr(docs), _ptr(scores)))
+        return docs, scores
+
+    def search_weighted_device(self, d_queries, d_weights, k: int, d_masks, d_query_mask, d_docs,
+                               d_scores, stream=None) -> None:
+        """Device-resident search_weighted (bm25_search_weighted_device): torch
+        int32 [Q, T] queries, float32 [Q, T] weights, packed masks [M, W] (or
+        None: no masks) and int32 [Q] mask ids (or None: mask 0 for every
+        query; without masks, no filter) in, int32 / float32 [Q, k] out,
+        enqueued on ``stream``.  No validation: token ids >= n_terms are
+        padding, the weights of non-padding slots must be finite and the mask
+        ids in [-1, M).  It may synchronise ``stream`` once, as
+        search_filtered_device."""
+        if d_queries.dim() != 2:
+            raise ValueError("d_queries must be a 2-D [Q, T] tensor")
+        Q, T = d_queries.shape
+        if (tuple(d_weights.shape) != (Q, T) or not d_weights.dtype.is_floating_point
+                or d_weights.element_size() != 4):
+            raise ValueError(f"d_weights must be a float32 [{Q}, {T}] tensor")
+        W = (self.n_docs + 31) // 32
+        M = 0
+        if d_masks is not None:
+            if d_masks.dim() != 2 or d_masks.shape[1] != W or d_masks.element_size() != 4:
+                raise ValueError(f"d_masks must be a packed [M, {W}] tensor of 32-bit words")
+            M = d_masks.shape[0]
+        if d_query_mask is not None and d_query_mask.numel() != Q:
+            raise ValueError(f"d_query_mask must hold one mask id per query ({Q})")
+        k = int(k)
+        if d_docs.numel() != Q * k or d_scores.numel() != Q * k:
+            raise ValueError(f"d_docs and d_scores must hold {Q} x {k} results")
+        s = getattr(stream, "cuda_stream", stream) or 0
+        qm = None if d_query_mask is None else ctypes.c_void_p(d_query_mask.data_ptr())
+        check(lib.bm25_search_weighted_device(
+            self._h, ctypes.c_void_p(d_queries.data_ptr()), ctypes.c_void_p(d_weights.data_ptr()),
+            Q, T, k, ctypes.c_void_p(d_masks.data_ptr()) if M else None, M, qm,
+            ctypes.c_void_p(d_docs.data_ptr()), ctypes.c_void_p(d_scores.data_ptr()),
+            ctypes.c_void_p(s)))
+
+    def score_docs_weighted(self, queries, weights, docs) -> np.ndarray:
+        """score_docs under weighted query terms (bm25_score_docs_weighted,
+        host arrays): out[q, c] is bit for bit the score search_weighted
+        reports for docs[q, c] under (queries[q], weights[q])."""
+        q = np.ascontiguousarray(queries, dtype=np.int32)
+        d = np.ascontiguousarray(docs, dtype=np.int32)
+        if q.ndim != 2:
+            raise ValueError("queries must be a 2-D [Q, T] int32 array")
+        w = self._weights_arg(q, weights)
+        if d.ndim != 2:
+            raise ValueError("docs must be a 2-D [Q, C] int32 array")
+        if q.shape[0] != d.shape[0]:
+            raise ValueError(f"queries has {q.shape[0]} rows, docs has {d.shape[0]}")
+        out = np.zeros(d.shape, np.float32)
+        check(lib.bm25_score_docs_weighted(self._h, _ptr(q), _ptr(w), q.shape[0], q.shape[1],
+                                           _ptr(d), d.shape[1], _ptr(out)))
+        return out
+
+    def score_docs_weighted_device(self, d_queries, d_weights, d_docs, d_scores,
+                                   stream=None) -> None:
+        """Device-resident score_docs_weighted (bm25_score_docs_weighted_device):
+        as score_docs_device with float32 [Q, T] weights beside the queries —
+        no host synchronisation, no validation, the index arrays only; doc ids
+        outside this handle's range score +0.0, so doc shards add up."""
+        if d_queries.dim() != 2 or d_docs.dim() != 2:
+            raise ValueError("d_queries and d_docs must be 2-D [Q, T] and [Q, C] tensors")
+        Q, T = d_queries.shape
+        if (tuple(d_weights.shape) != (Q, T) or not d_weights.dtype.is_floating_point
+                or d_weights.element_size() != 4):
+            raise ValueError(f"d_weights must be a float32 [{Q}, {T}] tensor")
+        if d_docs.shape[0] != Q:
+            raise ValueError(f"d_queries has {Q} rows, d_docs has {d_docs.shape[0]}")
+        C = d_docs.shape[1]
+        if d_scores.numel() != Q * C:
+            raise ValueError(f"d_scores must hold {Q} x {C} scores")
+        s = getattr(stream, "cuda_stream", stream) or 0
+        check(lib.bm25_score_docs_weighted_device(
+            self._h, ctypes.c_void_p(d_queries.data_ptr()), ctypes.c_void_p(d_weights.data_ptr()),
+            Q, T, ctypes.c_void_p(d_docs.data_ptr()), C, ctypes.c_void_p(d_scores.data_ptr()),
+            ctypes.c_void_p(s)))
+
     # -------------------------------------------------- boolean term filters
     def _clauses_arg(self, must, any, must_not, base, rows=None):
         """The clause rows of term_masks / search_boolean: each of must, any,
@@ -575,9 +694,10 @@ class GpuIndex:
     KERNELS = {1: "flat_sample", 2: "flat_rest", 4: "flat_all", 8: "wave_sample",
                16: "wave_rest", 32: "wave_all", 64: "large_k", 128: "bound_keys",
                256: "bound_off", 512: "count_skips", 1024: "rest_split",
-               2048: "bound_pool", 4096: "filtered"}  # (flags, not
+               2048: "bound_pool", 4096: "filtered", 8192: "weighted"}  # (flags, not
     # kernels: 256 the tile-bound threshold was off, 512 REST counted the postings it
-    # skipped, 1024 REST ran over split items, 2048 the threshold read the pooled bounds)
+    # skipped, 1024 REST ran over split items, 2048 the threshold read the pooled bounds,
+    # 8192 the search was weighted)
 
     def last_dispatch(self) -> dict:
         """What the last search launched (bm25_search_dispatch): the score

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -465,7 +466,7 @@ int run_search(bm25_index* h, const int32_t* d_queries, int64_t Q, int64_t T, in
 // workspace, its stream ordering and the large-k scratch as run_search's.
 int run_filtered(bm25_index* h, const int32_t* d_queries, int64_t Q, int64_t T, int k,
                  const uint32_t* d_masks, int64_t M, const int32_t* d_query_mask, int32_t* d_docs,
-                 float* d_scores, hipStream_t st) {
+                 float* d_scores, hipStream_t st, const float* d_weights = nullptr) {
   if (Q == 0 || k == 0) return BM25_OK;
   const int rc = ensure_ws(h, Q, T, std::min<int>(k, kMaxK), st);
   if (rc) return rc;
@@ -488,8 +489,8 @@ int run_filtered(bm25_index* h, const int32_t* d_queries, int64_t Q, int64_t T, 
   if (ev) HIP_TRY(hipEventRecord(ev->a, st), "hipEventRecord");
   int64_t nd = 0;
   HIP_TRY(launch_search_filtered(h->ix, d_queries, Q, T, k, d_masks, M, d_query_mask, h->ws,
-                                 d_docs, d_scores, &nd, st),
-          "filtered search");
+                                 d_docs, d_scores, &nd, st, d_weights),
+          d_weights ? "weighted search" : "filtered search");
   h->filtered_dense = nd;
   if (ev) {
     HIP_TRY(hipEventRecord(ev->b, st), "hipEventRecord");
@@ -537,6 +538,16 @@ int check_token_ids(int64_t n_terms, int64_t mx0, const int32_t* ids, int64_t n)
                 "The maximum token ID in the query (%lld) is higher than the number of tokens in "
                 "the index.",
                 (long long)mx);
+  return BM25_OK;
+}
+
+// The weighted calls' finite-weight rule: a weight on a non-padding slot (a
+// token id >= 0; ids >= n_terms were rejected before) must be finite.
+int check_weights(const int32_t* ids, const float* w, int64_t Q, int64_t T) {
+  for (int64_t i = 0; i < Q * T; ++i)
+    if (ids[i] >= 0 && !std::isfinite(w[i]))
+      return fail(BM25_EINVAL, "weights[%lld][%lld] = %g is not finite", (long long)(i / T),
+                  (long long)(i % T), (double)w[i]);
   return BM25_OK;
 }
 
@@ -921,6 +932,69 @@ int bm25_search_filtered_device(bm25_index* h, const int32_t* d_queries, int64_t
   if (in.rc) return in.rc;
   return run_filtered(h, d_queries, Q, T, k, d_masks, M, d_query_mask, d_docs, d_scores,
                       (hipStream_t)stream);
+}
+
+int bm25_search_weighted(bm25_index* h, const int32_t* queries, const float* weights, int64_t Q,
+                         int64_t T, int32_t k, const uint32_t* masks, int64_t M,
+                         const int32_t* query_mask, int32_t* out_docs, float* out_scores) {
+  if (!h) return fail(BM25_EINVAL, "NULL index");
+  if (Q < 0 || T < 0 || M < 0) return fail(BM25_EINVAL, "negative query or mask shape");
+  int rc = check_k(h, k);
+  if (rc) return rc;
+  if (Q == 0 || k == 0) return BM25_OK;
+  if (T > 0 && !queries) return fail(BM25_EINVAL, "NULL queries");
+  if (T > 0 && !weights) return fail(BM25_EINVAL, "NULL weights");
+  if (M > 0 && !masks) return fail(BM25_EINVAL, "NULL masks");
+  if (!out_docs || !out_scores) return fail(BM25_EINVAL, "NULL output");
+  rc = check_token_ids(h->ix.n_terms, 0, queries, Q * T);
+  if (rc) return rc;
+  rc = check_weights(queries, weights, Q, T);
+  if (rc) return rc;
+  if (query_mask)
+    for (int64_t i = 0; i < Q; ++i)
+      if (query_mask[i] < -1 || query_mask[i] >= M)
+        return fail(BM25_EINVAL, "query_mask[%lld] = %d is outside [-1, %lld)", (long long)i,
+                    query_mask[i], (long long)M);
+  Enter in(h);
+  if (in.rc) return in.rc;
+  rc = ensure_io(h, Q * T, Q * (int64_t)k);
+  if (rc) return rc;
+  // the weights, masks and mask ids: staging buffers of this call's own
+  const int64_t W = (h->ix.n_docs + 31) >> 5;
+  HostCall c(h->stream);
+  float* d_w = c.alloc<float>(Q * T);
+  uint32_t* d_masks = M > 0 ? c.alloc<uint32_t>(M * W) : nullptr;
+  int32_t* d_qm = query_mask ? c.alloc<int32_t>(Q) : nullptr;
+  c.upload_to(d_w, weights, Q * T);
+  c.upload_to(d_masks, masks, M * W);
+  if (query_mask) c.upload_to(d_qm, query_mask, Q);
+  c.upload_to(h->d_q, queries, Q * T);
+  if (!c.ok()) return c.finish("weighted search staging");
+  c.hold(run_filtered(h, h->d_q, Q, T, k, d_masks, M, d_qm, h->d_docs, h->d_scores, h->stream,
+                      d_w));
+  c.download(out_docs, h->d_docs, Q * k);
+  c.download(out_scores, h->d_scores, Q * k);
+  return c.finish("weighted search");
+}
+
+int bm25_search_weighted_device(bm25_index* h, const int32_t* d_queries, const float* d_weights,
+                                int64_t Q, int64_t T, int32_t k, const uint32_t* d_masks,
+                                int64_t M, const int32_t* d_query_mask, int32_t* d_docs,
+                                float* d_scores, void* stream) {
+  if (!h) return fail(BM25_EINVAL, "NULL index");
+  if (Q < 0 || T < 0 || M < 0) return fail(BM25_EINVAL, "negative query or mask shape");
+  int rc = check_k(h, k);
+  if (rc) return rc;
+  if (Q == 0 || k == 0) return BM25_OK;
+  if (T > 0 && (!d_queries || !d_weights)) return fail(BM25_EINVAL, "NULL queries or weights");
+  if (M > 0 && !d_masks) return fail(BM25_EINVAL, "NULL masks");
+  if (!d_docs || !d_scores) return fail(BM25_EINVAL, "NULL output");
+  Enter in(h);
+  if (in.rc) return in.rc;
+  // T == 0: no weight is read, but the weighted path still wants a pointer
+  static const float none = 0.f;
+  return run_filtered(h, d_queries, Q, T, k, d_masks, M, d_query_mask, d_docs, d_scores,
+                      (hipStream_t)stream, d_weights ? d_weights : &none);
 }
 
 int bm25_search_filtered_stats(bm25_index* h, int64_t* out, int32_t n) {
@@ -1428,6 +1502,60 @@ int bm25_score_docs_device(bm25_index* h, const int32_t* d_queries, int64_t Q, i
   if (in.rc) return in.rc;
   HIP_TRY(launch_score_docs(h->ix, d_queries, Q, T, d_docs, C, d_scores, (hipStream_t)stream),
           "score_docs launch");
+  return BM25_OK;
+}
+
+int bm25_score_docs_weighted(bm25_index* h, const int32_t* queries, const float* weights,
+                             int64_t Q, int64_t T, const int32_t* docs, int64_t C,
+                             float* out_scores) {
+  if (!h) return fail(BM25_EINVAL, "NULL index");
+  if (Q < 0 || T < 0 || C < 0) return fail(BM25_EINVAL, "negative query or candidate shape");
+  if (Q == 0 || C == 0) return BM25_OK;
+  if (T > 0 && !queries) return fail(BM25_EINVAL, "NULL queries");
+  if (T > 0 && !weights) return fail(BM25_EINVAL, "NULL weights");
+  if (!docs) return fail(BM25_EINVAL, "NULL docs");
+  if (!out_scores) return fail(BM25_EINVAL, "NULL output");
+  int rc = check_token_ids(h->ix.n_terms, 0, queries, Q * T);
+  if (rc) return rc;
+  rc = check_weights(queries, weights, Q, T);
+  if (rc) return rc;
+  const int64_t lo = h->ix.doc_offset, hi = h->ix.doc_offset + h->ix.n_docs;
+  for (int64_t i = 0; i < Q * C; ++i)
+    if (docs[i] >= 0 && (docs[i] < lo || docs[i] >= hi))
+      return fail(BM25_EINVAL, "doc id %lld (row %lld) is outside the index's documents [%lld, %lld)",
+                  (long long)docs[i], (long long)(i / C), (long long)lo, (long long)hi);
+  Enter in(h);
+  if (in.rc) return in.rc;
+  // staging buffers of this call's own (as bm25_score_docs)
+  HostCall c(h->stream);
+  int32_t* d_qq = c.alloc<int32_t>(Q * T);
+  float* d_ww = c.alloc<float>(Q * T);
+  int32_t* d_dd = c.alloc<int32_t>(Q * C);
+  float* d_out = c.alloc<float>(Q * C);
+  c.upload_to(d_qq, queries, Q * T);
+  c.upload_to(d_ww, weights, Q * T);
+  c.upload_to(d_dd, docs, Q * C);
+  if (c.ok()) c.run(launch_score_docs(h->ix, d_qq, Q, T, d_dd, C, d_out, h->stream, d_ww));
+  c.download(out_scores, d_out, Q * C);
+  return c.finish("score_docs_weighted");
+}
+
+int bm25_score_docs_weighted_device(bm25_index* h, const int32_t* d_queries,
+                                    const float* d_weights, int64_t Q, int64_t T,
+                                    const int32_t* d_docs, int64_t C, float* d_scores,
+                                    void* stream) {
+  if (!h) return fail(BM25_EINVAL, "NULL index");
+  if (Q < 0 || T < 0 || C < 0) return fail(BM25_EINVAL, "negative query or candidate shape");
+  if (Q == 0 || C == 0) return BM25_OK;
+  if (T > 0 && (!d_queries || !d_weights)) return fail(BM25_EINVAL, "NULL queries or weights");
+  if (!d_docs || !d_scores) return fail(BM25_EINVAL, "NULL docs or output");
+  // (as bm25_score_docs_device: the index arrays only, no ordering, no wait)
+  Enter in(h);
+  if (in.rc) return in.rc;
+  // T == 0: every score is +0.0f either way (no weight is read)
+  HIP_TRY(launch_score_docs(h->ix, d_queries, Q, T, d_docs, C, d_scores, (hipStream_t)stream,
+                            T > 0 ? d_weights : nullptr),
+          "score_docs_weighted launch");
   return BM25_OK;
 }
 

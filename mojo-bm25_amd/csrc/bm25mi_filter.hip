@@ -27,6 +27,12 @@
 //            whose theta is a zero-score key) take the dense path of
 //            bm25mi_large.hip on their own, as does every query when k > kMaxK
 //            or the filter_tiles option is 0
+//
+// The weighted search (bm25_search_weighted) is this pass with a weight row
+// beside every query row: add_item's weighted instantiation multiplies each
+// posting by its term's weight before the add.  Nothing above
+// relies on a tile bound or on the values' sign, which is what weights of
+// either sign need.
 #include "bm25mi_internal.h"
 
 namespace bm25mi {
@@ -175,7 +181,7 @@ hipError_t launch_search_filtered(const DevIndex& ix, const int32_t* d_queries, 
                                   int64_t T, int k, const uint32_t* d_masks, int64_t M,
                                   const int32_t* d_query_mask, const Workspace& ws,
                                   int32_t* d_docs, float* d_scores, int64_t* n_dense,
-                                  hipStream_t st) {
+                                  hipStream_t st, const float* d_weights) {
   *n_dense = 0;
   if (Q == 0 || k == 0) return hipSuccess;
   if (k > ix.n_docs) return hipErrorInvalidValue;
@@ -183,6 +189,17 @@ hipError_t launch_search_filtered(const DevIndex& ix, const int32_t* d_queries, 
   Scratch sc(st, ws.arena);
   int32_t* census = nullptr;
   uint32_t* total = nullptr;
+  if (d_weights) {
+    ix.disp.kernels |= kKWeighted;
+    // the weighted search without masks and mask ids: no filter for every
+    // query, as mask ids of -1 (the kernels read a null d_query_mask as mask 0)
+    if (M == 0 && !d_query_mask) {
+      int32_t* none = nullptr;
+      FL_TRY(sc.get(&none, Q));
+      FL_TRY(hipMemsetAsync(none, 0xFF, sizeof(int32_t) * Q, st));
+      d_query_mask = none;
+    }
+  }
   FL_TRY(sc.get(&census, M * ix.ntiles));
   FL_TRY(sc.get(&total, M));
   if (M > 0) {
@@ -193,15 +210,15 @@ hipError_t launch_search_filtered(const DevIndex& ix, const int32_t* d_queries, 
   if (!ix.opt.filter_tiles || k > kMaxK) {
     *n_dense = Q;
     return launch_search_filtered_dense(ix, d_queries, T, k, d_masks, d_query_mask, total, nullptr,
-                                        Q, d_docs, d_scores, st, ws.arena);
+                                        Q, d_docs, d_scores, st, ws.arena, d_weights);
   }
   ix.disp.kernels |= kKFiltered;
   FL_TRY(launch_filter_pass_a(ix, d_queries, Q, T, d_masks, d_query_mask, census, ws.cand,
-                              ws.counters + 5, st));
+                              ws.counters + 5, st, d_weights));
   hipLaunchKernelGGL(filter_theta_kernel, dim3((unsigned)Q), dim3(kFinT), 0, st, ws.cand,
                      ix.ntiles * kTileM, (uint32_t)k, ws.theta, ws.list_cnt);
   FL_TRY(launch_filter_pass_b(ix, d_queries, Q, T, d_masks, d_query_mask, ws.cand, ws.theta,
-                              ws.list, ws.list_cnt, ws.list_cap, ws.counters + 3, st));
+                              ws.list, ws.list_cnt, ws.list_cap, ws.counters + 3, st, d_weights));
   hipLaunchKernelGGL(filter_finish_kernel, dim3((unsigned)Q), dim3(kFinT), 0, st, ws.list,
                      ws.list_cnt, ws.list_cap, (int32_t)k, ix.doc_offset, d_docs, d_scores,
                      ws.slow, ws.counters + 2);
@@ -214,7 +231,7 @@ hipError_t launch_search_filtered(const DevIndex& ix, const int32_t* d_queries, 
   *n_dense = nfb;
   if (nfb == 0) return hipSuccess;
   return launch_search_filtered_dense(ix, d_queries, T, k, d_masks, d_query_mask, total, ws.slow,
-                                      nfb, d_docs, d_scores, st, ws.arena);
+                                      nfb, d_docs, d_scores, st, ws.arena, d_weights);
 }
 
 }  // namespace bm25mi

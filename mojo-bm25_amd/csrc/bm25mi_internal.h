@@ -105,6 +105,7 @@ enum {
   kKRestSplit = 1024,  // (a flag) REST ran over split items (heavy queries' bands in pieces)
   kKBoundPool = 2048,  // (a flag) the tile-bound threshold came from the pooled bounds
   kKFiltered = 4096,   // the filtered search's tile passes (bm25mi_filter.hip)
+  kKWeighted = 8192,   // (a flag) the search was weighted (bm25_search_weighted)
 };
 struct Dispatch {
   uint32_t kernels = 0;       // kK* bits of the score kernels launched
@@ -368,9 +369,11 @@ hipError_t launch_scores_dense(const DevIndex& ix, const int32_t* d_query,
 // (d_queries[q][*], d_docs[q * C + c]) — element d_docs[..] - doc_offset of
 // launch_scores_dense's row.  d_docs holds global ids; a negative id or one
 // outside [doc_offset, doc_offset + n_docs) scores +0.0f.  Reads the index
-// arrays only (no workspace).
+// arrays only (no workspace).  d_weights [Q][T] (or null): every value found
+// enters as the fp32 product weight * value (bm25_score_docs_weighted).
 hipError_t launch_score_docs(const DevIndex& ix, const int32_t* d_queries, int64_t Q, int64_t T,
-                             const int32_t* d_docs, int64_t C, float* d_out, hipStream_t stream);
+                             const int32_t* d_docs, int64_t C, float* d_out, hipStream_t stream,
+                             const float* d_weights = nullptr);
 // W lists [Q, k] at element w * rank_stride (docs and scores alike) -> [Q, k];
 // sorted: every list is already best-first (W-way merge instead of a sort).
 hipError_t launch_merge_lists(const int32_t* d_docs, const float* d_scores,
@@ -379,9 +382,11 @@ hipError_t launch_merge_lists(const int32_t* d_docs, const float* d_scores,
 
 // Dense scores of G queries (rows of T terms) into d_out[g * stride + doc];
 // stride >= ntiles << tile_shift (whole tiles are stored; docs past n_docs
-// hold 0).  G <= 65535.
+// hold 0).  G <= 65535.  d_weights [G][T] (or null): the terms' weights of the
+// weighted search, every posting entering as the fp32 product weight * value.
 hipError_t launch_scores_batch(const DevIndex& ix, const int32_t* d_queries, int64_t G, int64_t T,
-                               int64_t stride, float* d_out, hipStream_t stream);
+                               int64_t stride, float* d_out, hipStream_t stream,
+                               const float* d_weights = nullptr);
 
 // Exact top-k for any k (the path of k > kMaxK, bm25mi_large.hip): per chunk
 // of queries the dense scores, a radix selection of the k-th key, the keys
@@ -429,7 +434,10 @@ hipError_t launch_merge_large(const int32_t* d_docs, const float* d_scores, int6
 // ceil(n_docs / 32), bit d & 31 of word d >> 5 = handle-local document d;
 // d_query_mask [Q] picks each query's mask (-1: no filter; null: mask 0 for
 // every query).  No kernel reads a mask word at index >= W, and bits at or
-// past n_docs never count.
+// past n_docs never count.  d_weights [Q][T] (or null) makes the search the
+// weighted one (bm25_search_weighted): every launch below scores with the
+// fp32 products weight * value in place of the values; then M == 0 with a null
+// d_query_mask means no filter for every query.
 //
 // The tile passes (bm25mi_kernels.hip): the allowed documents of every (mask,
 // tile) into d_census[M][ntiles] and of every mask into d_total[M] (zeroed by
@@ -443,12 +451,12 @@ hipError_t launch_filter_census(const DevIndex& ix, const uint32_t* d_masks, int
 hipError_t launch_filter_pass_a(const DevIndex& ix, const int32_t* d_queries, int64_t Q, int64_t T,
                                 const uint32_t* d_masks, const int32_t* d_query_mask,
                                 const int32_t* d_census, uint64_t* d_cand, int32_t* d_skipped,
-                                hipStream_t stream);
+                                hipStream_t stream, const float* d_weights = nullptr);
 hipError_t launch_filter_pass_b(const DevIndex& ix, const int32_t* d_queries, int64_t Q, int64_t T,
                                 const uint32_t* d_masks, const int32_t* d_query_mask,
                                 const uint64_t* d_cand, const uint64_t* d_theta, uint64_t* d_list,
                                 int32_t* d_list_cnt, int32_t C, int32_t* d_rescored,
-                                hipStream_t stream);
+                                hipStream_t stream, const float* d_weights = nullptr);
 // The dense path (bm25mi_large.hip), exact for every k, index and mask: per
 // chunk of queries the dense scores, the radix selection with the mask
 // applied where keys are formed and k_q = min(k, allowed documents of the
@@ -460,7 +468,8 @@ hipError_t launch_search_filtered_dense(const DevIndex& ix, const int32_t* d_que
                                         int k, const uint32_t* d_masks,
                                         const int32_t* d_query_mask, const uint32_t* d_total,
                                         const int32_t* d_ids, int64_t nq, int32_t* d_docs,
-                                        float* d_scores, hipStream_t stream, LargeArena* arena);
+                                        float* d_scores, hipStream_t stream, LargeArena* arena,
+                                        const float* d_weights = nullptr);
 // The whole filtered search (bm25mi_filter.hip): the census, then the tile
 // passes (k <= kMaxK and the filter_tiles option), theta, the lists' sort and
 // padded write, and the dense path for the queries whose list overflowed —
@@ -473,7 +482,7 @@ hipError_t launch_search_filtered(const DevIndex& ix, const int32_t* d_queries, 
                                   int64_t T, int k, const uint32_t* d_masks, int64_t M,
                                   const int32_t* d_query_mask, const Workspace& ws,
                                   int32_t* d_docs, float* d_scores, int64_t* n_dense,
-                                  hipStream_t stream);
+                                  hipStream_t stream, const float* d_weights = nullptr);
 
 // Boolean term filters as allow-masks (bm25mi_termmask.hip): d_out[M][W] in
 // the layout above, row m = the documents d < n_docs that d_base allows

@@ -142,6 +142,9 @@ __device__ __forceinline__ int64_t lane_i64(int64_t v, int l) {
   return (int64_t)(((uint64_t)hi << 32) | lo);
 }
 __device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ float lane_f32(float v, int l) {
+  return __uint_as_float(lane_u32(__float_as_uint(v), l));
+}
 
 // Max over the 64 lanes of a wave: DPP inside each 16-lane row, then the four
 // row results through SGPRs.
@@ -216,6 +219,13 @@ __device__ __forceinline__ void lds_add(float* p, float v) {
   __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
+// w * v rounded to fp32 on its own (the weighted searches' product, DESIGN.md
+// §4): never contracted with an add that follows.
+__device__ __forceinline__ float mul_rn(float w, float v) {
+#pragma clang fp contract(off)
+  return w * v;
+}
+
 // ---------------------------------------------------------------------------
 // Scatter phase of one item: acc[slot(d)] += the query terms' scores of doc d,
 // term by term in query order.  Replaces doc_toks[:, query].sum(axis=1)
@@ -231,10 +241,15 @@ __device__ __forceinline__ void lds_add(float* p, float v) {
 // happen in term order.  Inside a row, two lanes of one term never share a doc
 // (a CSC column holds a doc once); a row that spans a term boundary is issued
 // once per term under an exec mask.
+//
+// WT (the weighted search, bm25_search_weighted): lane s also holds the
+// weight wt of term s, and every posting of term s adds mul_rn(wt(s), value).
+// The term of a row, or of a row's part, is wave-uniform (sf, sc), so its
+// weight is one lane read; the rows' bookkeeping does not see the weights.
 // ---------------------------------------------------------------------------
-template <int S>
-__device__ __forceinline__ void add_group(const IndexArgs& a, int64_t beg, uint32_t len, int ng,
-                                          float* acc) {
+template <int S, bool WT = false>
+__device__ __forceinline__ void add_group(const IndexArgs& a, int64_t beg, uint32_t len, float wt,
+                                          int ng, float* acc) {
   const int lane = lane_id();
   const uint32_t incl = wave_incl_scan(len);
   const uint32_t start = incl - len;                // lane s: stream position of term s
@@ -281,24 +296,38 @@ __device__ __forceinline__ void add_group(const IndexArgs& a, int64_t beg, uint3
       if (sf[j] < 0) break;
       const bool live = r0 + 64u * j + lane < total;
       if (sf[j] == sl[j]) {
-        if (live) lds_add(acc + (dl[j] >> 2), v[j]);
+        if constexpr (WT) {
+          const float w = lane_f32(wt, sf[j]);
+          if (live) lds_add(acc + (dl[j] >> 2), mul_rn(w, v[j]));
+        } else {
+          if (live) lds_add(acc + (dl[j] >> 2), v[j]);
+        }
       } else {
-        for (int sc = sf[j]; sc <= sl[j]; ++sc)
-          if (live && ts[j] == sc) lds_add(acc + (dl[j] >> 2), v[j]);
+        for (int sc = sf[j]; sc <= sl[j]; ++sc) {
+          if constexpr (WT) {
+            const float w = lane_f32(wt, sc);
+            if (live && ts[j] == sc) lds_add(acc + (dl[j] >> 2), mul_rn(w, v[j]));
+          } else {
+            if (live && ts[j] == sc) lds_add(acc + (dl[j] >> 2), v[j]);
+          }
+        }
       }
     }
   }
 }
 
-// All query terms of one item, in groups of 64 (one term per lane).
-template <int S>
+// All query terms of one item, in groups of 64 (one term per lane).  WT: the
+// terms' weights wts[0..T) beside them; a padding slot's weight is not read.
+template <int S, bool WT = false>
 __device__ __forceinline__ void add_item(const IndexArgs& a, int64_t tile,
-                                         const int32_t* __restrict__ qterms, int T, float* acc) {
+                                         const int32_t* __restrict__ qterms, int T, float* acc,
+                                         const float* __restrict__ wts = nullptr) {
   const int lane = lane_id();
   for (int g0 = 0; g0 < T; g0 += kGroup) {
     const int ng = min(kGroup, T - g0);
     int64_t beg = 0;
     uint32_t len = 0;
+    float wt = 0.f;
     if (lane < ng) {
       const int32_t term = qterms[g0 + lane];
       if (term >= 0 && term < a.V) {  // negative ids are padding (bm25_native.py:151)
@@ -306,9 +335,10 @@ __device__ __forceinline__ void add_item(const IndexArgs& a, int64_t tile,
         segment(a, term, tile, r0, r1);
         beg = a.indptr[term] + r0;
         len = r1 - r0;
+        if constexpr (WT) wt = wts[g0 + lane];
       }
     }
-    add_group<S>(a, beg, len, ng, acc);
+    add_group<S, WT>(a, beg, len, wt, ng, acc);
   }
 }
 
@@ -1707,16 +1737,17 @@ __global__ __launch_bounds__(64) void scores_dense_kernel(IndexArgs a,
 // Dense per-doc scores of G queries at once (the large-k path,
 // bm25mi_large.hip): one wave per (tile, query), the whole tile stored to
 // out[g * stride + doc] (stride = ntiles << S: docs past n_docs hold 0).
-template <int S>
+template <int S, bool WT = false>
 __global__ __launch_bounds__(64) void scores_batch_kernel(IndexArgs a,
                                                           const int32_t* __restrict__ queries,
                                                           int32_t T, int64_t stride,
-                                                          float* __restrict__ out) {
+                                                          float* __restrict__ out,
+                                                          const float* __restrict__ weights) {
   constexpr int D = 1 << S, E = D / 64;
   __shared__ __attribute__((aligned(16))) float acc[D];
   const int64_t tile = blockIdx.x, g = blockIdx.y;
   zero_acc<S>(acc);
-  add_item<S>(a, tile, queries + g * T, T, acc);
+  add_item<S, WT>(a, tile, queries + g * T, T, acc, WT ? weights + g * T : nullptr);
   float fv[E];
   take_entries<S>(acc, fv);
   float* row = out + g * stride + (tile << S);
@@ -4109,12 +4140,19 @@ hipError_t launch_scores_dense(const DevIndex& ix, const int32_t* d_query, int64
 }
 
 hipError_t launch_scores_batch(const DevIndex& ix, const int32_t* d_queries, int64_t G, int64_t T,
-                               int64_t stride, float* d_out, hipStream_t stream) {
+                               int64_t stride, float* d_out, hipStream_t stream,
+                               const float* d_weights) {
   if (ix.ntiles == 0 || G == 0) return hipSuccess;
   if (ix.tile_shift != BM25_TILE_SHIFT || G > 65535 || stride < (ix.ntiles << ix.tile_shift))
     return hipErrorInvalidValue;
-  hipLaunchKernelGGL(scores_batch_kernel<BM25_TILE_SHIFT>, dim3((unsigned)ix.ntiles, (unsigned)G),
-                     dim3(64), 0, stream, args_of(ix), d_queries, (int32_t)T, stride, d_out);
+  constexpr int S = BM25_TILE_SHIFT;
+  const dim3 grid((unsigned)ix.ntiles, (unsigned)G);
+  if (d_weights)
+    hipLaunchKernelGGL((scores_batch_kernel<S, true>), grid, dim3(64), 0, stream, args_of(ix),
+                       d_queries, (int32_t)T, stride, d_out, d_weights);
+  else
+    hipLaunchKernelGGL((scores_batch_kernel<S>), grid, dim3(64), 0, stream, args_of(ix), d_queries,
+                       (int32_t)T, stride, d_out, d_weights);
   return hipGetLastError();
 }
 
@@ -4221,10 +4259,11 @@ __device__ __forceinline__ int32_t filter_mask_of(const FilterArgs& f, int64_t q
 // into cand[q][tile][kTileM] (handle-local doc ids; key 0: none).  A tile
 // whose census is 0 reads no posting.  Disallowed entries get the score bits
 // 0xFFFFFFFF, whose key is 0 (select_top's empty slot).
-template <int S>
+template <int S, bool WT = false>
 __global__ __launch_bounds__(64 * kWaves) void filter_pass_a_kernel(
     IndexArgs a, const int32_t* __restrict__ queries, int32_t T, int64_t nq, FilterArgs f,
-    uint64_t* __restrict__ cand, int32_t* __restrict__ skipped) {
+    uint64_t* __restrict__ cand, int32_t* __restrict__ skipped,
+    const float* __restrict__ weights) {
   constexpr int D = 1 << S;
   __shared__ __attribute__((aligned(16))) float acc_all[kWaves * D];
   const int wave = uniform((int)(threadIdx.x >> 6));
@@ -4252,7 +4291,7 @@ __global__ __launch_bounds__(64 * kWaves) void filter_pass_a_kernel(
     }
     const uint64_t allow = lane_allow<S>(m >= 0 ? f.masks + (int64_t)m * f.W : nullptr, f.W, tile,
                                          a.n_docs);
-    add_item<S>(a, tile, queries + q * T, T, acc);
+    add_item<S, WT>(a, tile, queries + q * T, T, acc, WT ? weights + q * T : nullptr);
     float fv[D / 64];
     take_entries<S>(acc, fv);
 #pragma unroll
@@ -4268,12 +4307,12 @@ __global__ __launch_bounds__(64 * kWaves) void filter_pass_a_kernel(
 // (one atomic per wave; a list past its capacity C only counts, as
 // emit_above's).  No other tile holds such a key.  A wave looks at 64 pairs
 // at a time (query-major: the 64 keys it tests are near each other).
-template <int S>
+template <int S, bool WT = false>
 __global__ __launch_bounds__(64 * kWaves) void filter_pass_b_kernel(
     IndexArgs a, const int32_t* __restrict__ queries, int32_t T, int64_t nq, FilterArgs f,
     const uint64_t* __restrict__ cand, const uint64_t* __restrict__ theta,
     uint64_t* __restrict__ list, int32_t* __restrict__ list_cnt, int32_t C,
-    int32_t* __restrict__ rescored) {
+    int32_t* __restrict__ rescored, const float* __restrict__ weights) {
   constexpr int D = 1 << S;
   constexpr int E = D / 64;
   __shared__ __attribute__((aligned(16))) float acc_all[kWaves * D];
@@ -4301,7 +4340,7 @@ __global__ __launch_bounds__(64 * kWaves) void filter_pass_b_kernel(
       const uint64_t th = theta[q];
       const uint64_t allow = lane_allow<S>(m >= 0 ? f.masks + (int64_t)m * f.W : nullptr, f.W,
                                            tile, a.n_docs);
-      add_item<S>(a, tile, queries + q * T, T, acc);
+      add_item<S, WT>(a, tile, queries + q * T, T, acc, WT ? weights + q * T : nullptr);
       float fv[E];
       take_entries<S>(acc, fv);
       const int64_t base = tile << S;
@@ -4349,17 +4388,25 @@ static FilterArgs filter_args(const DevIndex& ix, const uint32_t* d_masks,
 hipError_t launch_filter_pass_a(const DevIndex& ix, const int32_t* d_queries, int64_t Q, int64_t T,
                                 const uint32_t* d_masks, const int32_t* d_query_mask,
                                 const int32_t* d_census, uint64_t* d_cand, int32_t* d_skipped,
-                                hipStream_t stream) {
+                                hipStream_t stream, const float* d_weights) {
   if (Q == 0 || ix.ntiles == 0) return hipSuccess;
   if (ix.tile_shift != BM25_TILE_SHIFT) return hipErrorInvalidValue;
   constexpr int S = BM25_TILE_SHIFT;
   // (a multiple of 8: one share of the workgroups per XCD)
   const int64_t need = ((Q * ix.ntiles + 8 * kWaves - 1) / (8 * kWaves)) * 8;
+  const FilterArgs f = filter_args(ix, d_masks, d_query_mask, d_census);
+  if (d_weights) {
+    const int grid = (int)std::min<int64_t>(
+        need, persistent_grid(filter_pass_a_kernel<S, true>, 64 * kWaves));
+    hipLaunchKernelGGL((filter_pass_a_kernel<S, true>), dim3((unsigned)grid), dim3(64 * kWaves), 0,
+                       stream, args_of(ix), d_queries, (int32_t)T, Q, f, d_cand, d_skipped,
+                       d_weights);
+    return hipGetLastError();
+  }
   const int grid =
       (int)std::min<int64_t>(need, persistent_grid(filter_pass_a_kernel<S>, 64 * kWaves));
   hipLaunchKernelGGL((filter_pass_a_kernel<S>), dim3((unsigned)grid), dim3(64 * kWaves), 0, stream,
-                     args_of(ix), d_queries, (int32_t)T, Q,
-                     filter_args(ix, d_masks, d_query_mask, d_census), d_cand, d_skipped);
+                     args_of(ix), d_queries, (int32_t)T, Q, f, d_cand, d_skipped, d_weights);
   return hipGetLastError();
 }
 
@@ -4367,17 +4414,25 @@ hipError_t launch_filter_pass_b(const DevIndex& ix, const int32_t* d_queries, in
                                 const uint32_t* d_masks, const int32_t* d_query_mask,
                                 const uint64_t* d_cand, const uint64_t* d_theta, uint64_t* d_list,
                                 int32_t* d_list_cnt, int32_t C, int32_t* d_rescored,
-                                hipStream_t stream) {
+                                hipStream_t stream, const float* d_weights) {
   if (Q == 0 || ix.ntiles == 0) return hipSuccess;
   if (ix.tile_shift != BM25_TILE_SHIFT) return hipErrorInvalidValue;
   constexpr int S = BM25_TILE_SHIFT;
   const int64_t need = (Q * ix.ntiles + 64 * kWaves - 1) / (64 * kWaves);
+  const FilterArgs f = filter_args(ix, d_masks, d_query_mask, nullptr);
+  if (d_weights) {
+    const int grid = (int)std::min<int64_t>(
+        need, persistent_grid(filter_pass_b_kernel<S, true>, 64 * kWaves));
+    hipLaunchKernelGGL((filter_pass_b_kernel<S, true>), dim3((unsigned)grid), dim3(64 * kWaves), 0,
+                       stream, args_of(ix), d_queries, (int32_t)T, Q, f, d_cand, d_theta, d_list,
+                       d_list_cnt, C, d_rescored, d_weights);
+    return hipGetLastError();
+  }
   const int grid =
       (int)std::min<int64_t>(need, persistent_grid(filter_pass_b_kernel<S>, 64 * kWaves));
   hipLaunchKernelGGL((filter_pass_b_kernel<S>), dim3((unsigned)grid), dim3(64 * kWaves), 0, stream,
-                     args_of(ix), d_queries, (int32_t)T, Q,
-                     filter_args(ix, d_masks, d_query_mask, nullptr), d_cand, d_theta, d_list,
-                     d_list_cnt, C, d_rescored);
+                     args_of(ix), d_queries, (int32_t)T, Q, f, d_cand, d_theta, d_list, d_list_cnt,
+                     C, d_rescored, d_weights);
   return hipGetLastError();
 }
 

@@ -938,7 +938,8 @@ hipError_t launch_search_filtered_dense(const DevIndex& ix, const int32_t* d_que
                                         int k, const uint32_t* d_masks,
                                         const int32_t* d_query_mask, const uint32_t* d_total,
                                         const int32_t* d_ids, int64_t nq, int32_t* d_docs,
-                                        float* d_scores, hipStream_t st, LargeArena* arena) {
+                                        float* d_scores, hipStream_t st, LargeArena* arena,
+                                        const float* d_weights) {
   if (nq == 0 || k == 0) return hipSuccess;
   if (k > ix.n_docs) return hipErrorInvalidValue;
   ix.disp.kernels |= kKLarge;
@@ -948,6 +949,7 @@ hipError_t launch_search_filtered_dense(const DevIndex& ix, const int32_t* d_que
   // scattered back
   const int32_t* q = d_queries;
   const int32_t* qm = d_query_mask;
+  const float* wq = d_weights;
   int32_t* od = d_docs;
   float* os = d_scores;
   if (d_ids) {
@@ -959,6 +961,14 @@ hipError_t launch_search_filtered_dense(const DevIndex& ix, const int32_t* d_que
       hipLaunchKernelGGL(gather_rows_kernel, dim3(grid_for(nq * T, 256, 4096)), dim3(256), 0, st,
                          d_queries, d_ids, nq, T, fq);
     q = fq;
+    if (d_weights) {  // the weight rows with them (4-byte elements: the same kernel)
+      int32_t* fw = nullptr;
+      LK_TRY(sc.get(&fw, nq * std::max<int64_t>(T, 1)));
+      if (T > 0)
+        hipLaunchKernelGGL(gather_rows_kernel, dim3(grid_for(nq * T, 256, 4096)), dim3(256), 0, st,
+                           reinterpret_cast<const int32_t*>(d_weights), d_ids, nq, T, fw);
+      wq = reinterpret_cast<const float*>(fw);
+    }
     if (d_query_mask) {
       LK_TRY(sc.get(&fm, nq));
       hipLaunchKernelGGL(gather_rows_kernel, dim3(grid_for(nq, 256, 4096)), dim3(256), 0, st,
@@ -994,7 +1004,7 @@ hipError_t launch_search_filtered_dense(const DevIndex& ix, const int32_t* d_que
   for (int64_t q0 = 0; q0 < nq; q0 += G) {
     const int64_t g = std::min<int64_t>(G, nq - q0);
     ma.qm = qm ? qm + q0 : nullptr;
-    LK_TRY(launch_scores_batch(ix, q + q0 * T, g, T, Np, scores, st));
+    LK_TRY(launch_scores_batch(ix, q + q0 * T, g, T, Np, scores, st, wq ? wq + q0 * T : nullptr));
     LK_TRY(hipMemsetAsync(keys, 0, sizeof(uint64_t) * g * k, st));
     hipLaunchKernelGGL(lk_init_kernel<true>, dim3(1), dim3(64), 0, st, state, g, (uint32_t)k, cnt,
                        ma);

@@ -22,6 +22,11 @@
 // and the wave holds 64 of them in flight.  The 2^TL values of a pair are then
 // added one by one from term slot 0 upward (the rounding sequence is the
 // contract: no tree reduction).
+//
+// The weighted form (bm25_score_docs_weighted) multiplies a value that was
+// found by its term's weight, rounded to fp32 on its own, before that sum:
+// the fold of bm25_search_weighted, so the bits agree with its scores.  A
+// posting that is absent adds +0.0f, not weight * 0.
 #include "bm25mi_internal.h"
 
 #include <algorithm>
@@ -46,8 +51,10 @@ struct LookupArgs {
 };
 
 // The index value of (term, local document id), both in range; +0.0f where the
-// document does not hold the term.
-__device__ __forceinline__ float posting_value(const LookupArgs& a, int64_t term, int64_t local) {
+// document does not hold the term (*found, if given, tells the two apart).
+__device__ __forceinline__ float posting_value(const LookupArgs& a, int64_t term, int64_t local,
+                                               bool* found = nullptr) {
+  if (found) *found = false;
   const int64_t tile = local >> a.tile_shift;
   const uint32_t slot = ((uint32_t)local & ((1u << a.tile_shift) - 1u)) << 2;
   const int64_t p0 = a.indptr[term];
@@ -76,17 +83,26 @@ __device__ __forceinline__ float posting_value(const LookupArgs& a, int64_t term
     if ((uint32_t)seg[mid] < slot) lo = mid + 1;
     else hi = mid;
   }
-  if (lo < r1 && (uint32_t)seg[lo] == slot) return a.val[p0 + lo];
+  if (lo < r1 && (uint32_t)seg[lo] == slot) {
+    if (found) *found = true;
+    return a.val[p0 + lo];
+  }
   return 0.f;
 }
 
 // Pairs g = q * C + c, 64 >> TL of them per wave step, grid-stride; the lanes
 // of a pair share g, so its shuffles stay inside wholly active groups (the
-// loops' trip counts are wave-uniform).
-template <int TL>
+// loops' trip counts are wave-uniform).  WT: weights [Q][T] beside the queries.
+__device__ __forceinline__ float weight_times(float w, float v) {
+#pragma clang fp contract(off)
+  return w * v;  // rounded on its own: never fused with the sum's add
+}
+
+template <int TL, bool WT = false>
 __global__ __launch_bounds__(kLookupNT) void score_docs_kernel(
     LookupArgs a, const int32_t* __restrict__ queries, int64_t T,
-    const int32_t* __restrict__ docs, int64_t C, int64_t n_pairs, float* __restrict__ out) {
+    const int32_t* __restrict__ docs, int64_t C, int64_t n_pairs, float* __restrict__ out,
+    const float* __restrict__ weights) {
   constexpr int G = 1 << TL;
   constexpr int kPerWave = 64 / G;
   const int lane = (int)(threadIdx.x & 63u);
@@ -98,11 +114,13 @@ __global__ __launch_bounds__(kLookupNT) void score_docs_kernel(
     const bool live = g < n_pairs;
     int64_t local = -1;
     const int32_t* qrow = queries;
+    const float* wrow = weights;
     if (live) {
       const int32_t doc = docs[g];
       // a negative id is padding; an id outside the handle's range scores +0.0f
       local = doc < 0 ? -1 : (int64_t)doc - a.doc_offset;
       qrow = queries + (g / C) * T;
+      if constexpr (WT) wrow = weights + (g / C) * T;
     }
     const bool have = local >= 0 && local < a.n_docs;
     float acc = 0.f;
@@ -110,7 +128,15 @@ __global__ __launch_bounds__(kLookupNT) void score_docs_kernel(
       float v = 0.f;
       if (have && t0 + j < T) {
         const int32_t term = qrow[t0 + j];
-        if (term >= 0 && (int64_t)term < a.V) v = posting_value(a, term, local);
+        if constexpr (WT) {
+          if (term >= 0 && (int64_t)term < a.V) {  // (a padding slot's weight is not read)
+            bool found;
+            const float x = posting_value(a, term, local, &found);
+            if (found) v = weight_times(wrow[t0 + j], x);
+          }
+        } else {
+          if (term >= 0 && (int64_t)term < a.V) v = posting_value(a, term, local);
+        }
       }
       const int n = T - t0 < G ? (int)(T - t0) : G;
       for (int i = 0; i < n; ++i) acc += __shfl(v, i, G);  // query order
@@ -122,7 +148,8 @@ __global__ __launch_bounds__(kLookupNT) void score_docs_kernel(
 }  // namespace
 
 hipError_t launch_score_docs(const DevIndex& ix, const int32_t* d_queries, int64_t Q, int64_t T,
-                             const int32_t* d_docs, int64_t C, float* d_out, hipStream_t st) {
+                             const int32_t* d_docs, int64_t C, float* d_out, hipStream_t st,
+                             const float* d_weights) {
   const int64_t n_pairs = Q * C;
   if (n_pairs == 0) return hipSuccess;
   if (ix.tile_shift < 1 || ix.tile_shift > 14) return hipErrorInvalidValue;  // (ldoc is u16)
@@ -143,9 +170,13 @@ hipError_t launch_score_docs(const DevIndex& ix, const int32_t* d_queries, int64
   // 8 workgroups (32 waves) per CU hold the chip; more pairs take more steps
   const unsigned grid = (unsigned)std::max<int64_t>(
       1, std::min<int64_t>((n_pairs + per_block - 1) / per_block, (int64_t)cus * 8));
-#define BM25_LOOKUP(TL_)                                                                        \
-  hipLaunchKernelGGL(score_docs_kernel<TL_>, dim3(grid), dim3(kLookupNT), 0, st, a, d_queries, T, \
-                     d_docs, C, n_pairs, d_out)
+#define BM25_LOOKUP(TL_)                                                                       \
+  if (d_weights)                                                                               \
+    hipLaunchKernelGGL((score_docs_kernel<TL_, true>), dim3(grid), dim3(kLookupNT), 0, st, a,  \
+                       d_queries, T, d_docs, C, n_pairs, d_out, d_weights);                    \
+  else                                                                                         \
+    hipLaunchKernelGGL((score_docs_kernel<TL_>), dim3(grid), dim3(kLookupNT), 0, st, a,        \
+                       d_queries, T, d_docs, C, n_pairs, d_out, d_weights)
   switch (tl) {
     case 3: BM25_LOOKUP(3); break;
     case 4: BM25_LOOKUP(4); break;
