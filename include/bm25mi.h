@@ -375,6 +375,79 @@ int bm25_score_docs_weighted_device(bm25_index* idx, const int32_t* d_queries,
                                     void* stream);
 
 /*
+ * Cursor pagination ("search after"): the next k results after a given
+ * (score, doc) pair — exact deep paging for export jobs, infinite scroll,
+ * rerankers that pull candidates until a budget is spent and doc shards that
+ * resume a scan — at the cost of a k-sized search instead of a search of the
+ * whole prefix.
+ * Replaces no reference call: BM25v.search has no cursor
+ * (bm25_native.py:76-158).
+ *   queries, weights, masks, M, query_mask, k, out_docs / out_scores: exactly
+ *              bm25_search_weighted(_device).  weights may be NULL: plain
+ *              sums, bit for bit what a row of 1.0f weights gives.  With
+ *              M == 0 a NULL query_mask means no filter for every query; with
+ *              M >= 1 NULL means mask 0; -1 = no filter for that row.
+ *              0 <= k <= n_docs.  Padding is doc -1 / score bits 0xFFFFFFFF.
+ *   after_scores [Q] f32, after_docs [Q] int32: one cursor (s, c) per query
+ *              row, c a global doc id.  A document d (handle-local, allowed by
+ *              the row's mask) is eligible iff
+ *                  score_key(score(q, d)) <  score_key(s), or
+ *                  score_key(score(q, d)) == score_key(s) and doc_offset + d > c
+ *              compared in 64 bits: a c outside [doc_offset, doc_offset +
+ *              n_docs) is legal and means what the inequality says, so every
+ *              doc shard of a collection searches after the collection's
+ *              cursor and the shards' lists merge through
+ *              bm25_merge_topk_device unchanged.  The cursor need not name an
+ *              existing or an allowed document.  Row q is the first k eligible
+ *              documents in the usual order (score descending, doc id
+ *              ascending), padded where fewer exist.
+ *              score_key is the engine's order of fp32 scores: the numeric
+ *              order, with -0.0f just below +0.0f.  Returned scores are never
+ *              -0.0f, so a cursor taken from a result never is.
+ *   after_docs[q] == BM25_AFTER_NONE (-2): no cursor; after_scores[q] is not
+ *              read and the row is bit for bit bm25_search_weighted's.
+ *   after_docs[q] == -1 (the doc id of a padding slot): the previous page ended
+ *              in padding, so the list is exhausted: the row is all padding
+ *              and no posting is read for it.  Feeding the last column of any
+ *              page back in is therefore always safe; -1 never means
+ *              "restart".
+ *   Both after_* pointers NULL: no cursor for every row.  Exactly one NULL:
+ *              BM25_EINVAL.
+ * The search takes the filtered search's passes with the cursor as one more
+ * per-document predicate (their threshold is an eligible document's own key,
+ * so they stay exact); the dense path clamps a row to its eligible documents.
+ * Every path gives the same bits.  A row with an exhausted cursor counts in
+ * bm25_search_filtered_stats [1] once per tile (pass A skips it as it skips an
+ * empty census).
+ *   bm25_search_after: host buffers, validated, synchronous.  Validates as
+ *     bm25_search_weighted (the finite-weight rule when weights are given),
+ *     plus: an after_docs entry < -2, and a NaN after_scores entry on a row
+ *     with after_docs >= 0, give BM25_EINVAL (the message names row and
+ *     value).
+ *   bm25_search_after_device: device buffers, enqueued on `stream`; checks
+ *     shapes and NULL pointers only.  An after_docs entry < -1 is "no cursor".
+ *     A row with a NaN cursor score has unspecified contents, the other rows
+ *     are unaffected and nothing outside the caller's buffers is read or
+ *     written (the rule of a non-finite weight).
+ * Both are searches of the handle: mutex, workspace, stream ordering, the one
+ * possible synchronisation, the retained scratch (plus 8 + 4 T bytes per query
+ * for the cursor keys and the query copy) and bm25_search_filtered_stats are
+ * as documented for bm25_search_filtered.  bm25_search_dispatch reports the
+ * flag 16384 after a search through either call, whatever its cursors, with
+ * 4096 / 64 / 8192 as the passes taken.
+ */
+#define BM25_AFTER_NONE (-2) /* after_docs[q]: no cursor, row q starts at rank 1 */
+int bm25_search_after(bm25_index* idx, const int32_t* queries, const float* weights, int64_t Q,
+                      int64_t T, int32_t k, const uint32_t* masks, int64_t M,
+                      const int32_t* query_mask, const float* after_scores,
+                      const int32_t* after_docs, int32_t* out_docs, float* out_scores);
+int bm25_search_after_device(bm25_index* idx, const int32_t* d_queries, const float* d_weights,
+                             int64_t Q, int64_t T, int32_t k, const uint32_t* d_masks, int64_t M,
+                             const int32_t* d_query_mask, const float* d_after_scores,
+                             const int32_t* d_after_docs, int32_t* d_docs, float* d_scores,
+                             void* stream);
+
+/*
  * Boolean term filters: the allow-masks of "+rust -java" — must contain all
  * of these terms, at least one of those, none of these — built on the device
  * from the index's own postings, in exactly the layout
@@ -733,7 +806,9 @@ int bm25_index_get_option(const bm25_index* idx, const char* name, int64_t* valu
  *                2048 (a flag): the threshold read the pooled bounds (bound_pool);
  *                4096: the filtered search's tile passes (its dense path sets 64);
  *                8192 (a flag): the last search was weighted
- *                (bm25_search_weighted; it sets 4096 and / or 64 as well)
+ *                (bm25_search_weighted; it sets 4096 and / or 64 as well);
+ *                16384 (a flag): the last search was called through
+ *                bm25_search_after(_device), whatever its cursors
  *   *term_lanes  flat kernel: term lanes per tile (8, 16, 32 or 64)
  *   band_tiles   [3]: flat kernel tiles per item of ALL, SAMPLE, REST
  *   *sample_p    sampling stride of the search (1: exact pass, 0: tile-bound

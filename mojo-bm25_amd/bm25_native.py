@@ -187,6 +187,55 @@ class BM25v:
             raise ValueError("BM25v index not built. Call index() first.")
         return self._gpu.search_weighted(queries, weights, top_k)
 
+    def search_after(self, queries, top_k: int, after=None, allow=None,
+                     weights=None) -> Tuple[np.ndarray, np.ndarray]:
+        """The next top_k results after a cursor (not in the reference, whose
+        search has no cursor): exact deep paging without searching the whole
+        prefix.  ``after`` is None (the first page) or the pair (scores [Q]
+        float32, docs [Q] int32) that bm25mi.page_cursor makes of the previous
+        page; a row whose previous page ended in padding (doc -1) comes back
+        all padding.  ``allow`` as in search_filtered, ``weights`` as in
+        search_weighted, both optional.  Returns search's tuple: doc ids
+        (int32) and scores (f32), [Q, top_k]."""
+        if len(queries) == 0:
+            return np.zeros((0, 0), dtype=self.dtype), np.zeros((0, 0), dtype=self.dtype)
+        if (not isinstance(queries, np.ndarray) or queries.ndim != 2
+                or not isinstance(queries[0][0], TokId)):
+            raise ValueError("The queries must be a list of list of query token IDs.")
+        Q = queries.shape[0]
+        if weights is not None:
+            weights = np.asarray(weights)
+            if weights.ndim != 2 or weights.shape != queries.shape:
+                raise ValueError(f"weights must be a float array of the queries' shape "
+                                 f"{queries.shape}, got shape {weights.shape}")
+        if allow is not None:
+            allow = np.asarray(allow)
+            if allow.ndim not in (1, 2) or (allow.ndim == 2 and allow.shape[0] != Q):
+                raise ValueError("allow must be a [n_docs] mask or a [Q, n_docs] array with one "
+                                 "row per query.")
+        if after is not None:
+            if not isinstance(after, (tuple, list)) or len(after) != 2 \
+                    or after[0] is None or after[1] is None:
+                raise ValueError("after must be None or a pair (scores [Q], docs [Q])")
+            if np.shape(after[0]) != (Q,) or np.shape(after[1]) != (Q,):
+                raise ValueError(f"after must hold one cursor per query ({Q})")
+            after = (np.ascontiguousarray(after[0], dtype=np.float32),
+                     np.ascontiguousarray(after[1], dtype=np.int32))
+        if top_k < 0:
+            raise ValueError("negative dimensions are not allowed")
+        max_token_id = int(queries.max(initial=0))
+        n_terms = self._gpu.n_terms if self._gpu is not None else len(self.doc_toks.indptr) - 1
+        if max_token_id >= n_terms:
+            raise ValueError(
+                f"The maximum token ID in the query ({max_token_id}) is higher than the number "
+                "of tokens in the index.")
+        if self._gpu is None:
+            raise ValueError("BM25v index not built. Call index() first.")
+        qm = None
+        if allow is not None:
+            qm = (np.zeros(Q, np.int32) if allow.ndim == 1 else np.arange(Q, dtype=np.int32))
+        return self._gpu.search_after(queries, top_k, after, weights, allow, qm)
+
     def search_boolean(self, queries, top_k: int, must=None, any=None, must_not=None,
                        base=None) -> Tuple[np.ndarray, np.ndarray]:
         """search under boolean term filters (not in the reference, whose

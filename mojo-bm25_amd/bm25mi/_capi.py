@@ -67,6 +67,10 @@ _SIGS = {
     "bm25_search_weighted": ([_P, _P, _P, _I64, _I64, _I32, _P, _I64, _P, _P, _P], ctypes.c_int),
     "bm25_search_weighted_device": ([_P, _P, _P, _I64, _I64, _I32, _P, _I64, _P, _P, _P, _P],
                                     ctypes.c_int),
+    "bm25_search_after": ([_P, _P, _P, _I64, _I64, _I32, _P, _I64, _P, _P, _P, _P, _P],
+                          ctypes.c_int),
+    "bm25_search_after_device": ([_P, _P, _P, _I64, _I64, _I32, _P, _I64, _P, _P, _P, _P, _P, _P],
+                                 ctypes.c_int),
     "bm25_score_docs_weighted": ([_P, _P, _P, _I64, _I64, _P, _I64, _P], ctypes.c_int),
     "bm25_score_docs_weighted_device": ([_P, _P, _P, _I64, _I64, _P, _I64, _P, _P],
                                         ctypes.c_int),

@@ -60,6 +60,26 @@ def pad_clause(rows) -> np.ndarray:
     return np.ascontiguousarray(rows, dtype=np.int32)
 
 
+AFTER_NONE = -2  # BM25_AFTER_NONE: an after-docs entry that means "no cursor"
+
+
+def page_cursor(docs, scores):
+    """The cursor after a page of results: its last column as the pair
+    (scores [Q] float32, docs [Q] int32) that search_after's ``after`` takes.
+    A row that ended in padding gives doc -1, which search_after reads as
+    "exhausted" (an all-padding row), so the last column of any page can be
+    fed back in.  Works on numpy arrays and on torch tensors (the device
+    call's outputs) alike."""
+    if docs.ndim != 2 or tuple(docs.shape) != tuple(scores.shape):
+        raise ValueError("docs and scores must be 2-D [Q, k] arrays of one shape")
+    if docs.shape[1] == 0:
+        raise ValueError("a page of k = 0 columns has no cursor")
+    if isinstance(docs, np.ndarray):
+        return (np.ascontiguousarray(scores[:, -1], dtype=np.float32),
+                np.ascontiguousarray(docs[:, -1], dtype=np.int32))
+    return scores[:, -1].contiguous(), docs[:, -1].contiguous()
+
+
 class GpuIndex:
     """A doc x term CSC score matrix resident in HBM.
 
@@ -491,6 +511,101 @@ class GpuIndex:
             ctypes.c_void_p(d_docs.data_ptr()), ctypes.c_void_p(d_scores.data_ptr()),
             ctypes.c_void_p(s)))
 
+    # ---------------------------------------------------- cursor pagination
+    def search_after(self, queries: np.ndarray, k: int, after=None, weights=None, masks=None,
+                     query_mask=None) -> Tuple[np.ndarray, np.ndarray]:
+        """The next k results after a cursor (bm25_search_after, host arrays):
+        ``after`` is None (no cursor: the first page) or a pair (scores [Q]
+        float32, docs [Q] int32) — page_cursor of the previous page — and row
+        q holds the first k documents strictly after (after_scores[q],
+        after_docs[q]) in the result order (score descending, doc id
+        ascending; global ids).  after_docs[q] == AFTER_NONE: no cursor for
+        that row; -1: the list is exhausted, the row is all padding.  weights
+        (None: plain sums), masks and query_mask as in search_weighted."""
+        q = np.ascontiguousarray(queries, dtype=np.int32)
+        if q.ndim != 2:
+            raise ValueError("queries must be a 2-D [Q, T] int32 array")
+        Q, T = q.shape
+        w = None if weights is None else self._weights_arg(q, weights)
+        m = None if masks is None else self._masks_arg(masks)
+        M = 0 if m is None else m.shape[0]
+        qm = None
+        if query_mask is not None:
+            qm = np.ascontiguousarray(query_mask, dtype=np.int32)
+            if qm.ndim != 1 or qm.size != Q:
+                raise ValueError(f"query_mask must hold one mask id per query ({Q}), "
+                                 f"got shape {qm.shape}")
+            if qm.size and (int(qm.min()) < -1 or int(qm.max()) >= M):
+                raise ValueError(f"query_mask entries must be in [-1, {M})")
+        a_s = a_d = None
+        if after is not None:
+            if not isinstance(after, (tuple, list)) or len(after) != 2:
+                raise ValueError("after must be None or a pair (scores [Q], docs [Q])")
+            if after[0] is None or after[1] is None:
+                raise ValueError("after needs both halves: (scores [Q], docs [Q])")
+            a_s, a_d = np.asarray(after[0]), np.asarray(after[1])
+            if a_s.dtype != np.float32 or a_d.dtype != np.int32:
+                raise ValueError("after must be (float32 scores, int32 docs): page_cursor's pair")
+            if a_s.shape != (Q,) or a_d.shape != (Q,):
+                raise ValueError(f"after must hold one cursor per query ({Q}), got shapes "
+                                 f"{a_s.shape} and {a_d.shape}")
+            a_s, a_d = np.ascontiguousarray(a_s), np.ascontiguousarray(a_d)
+            if a_d.size and int(a_d.min()) < AFTER_NONE:
+                raise ValueError(f"after docs must be >= AFTER_NONE ({AFTER_NONE})")
+            if bool((np.isnan(a_s) & (a_d >= 0)).any()):
+                raise ValueError("after scores must not be NaN where after docs name a document")
+        k = int(k)
+        docs = np.zeros((Q, max(k, 0)), np.int32)
+        scores = np.zeros((Q, max(k, 0)), np.float32)
+        check(lib.bm25_search_after(self._h, _ptr(q), _ptr(w), Q, T, k, _ptr(m) if M else None, M,
+                                    _ptr(qm), _ptr(a_s), _ptr(a_d), _ptr(docs), _ptr(scores)))
+        return docs, scores
+
+    def search_after_device(self, d_queries, k: int, d_after, d_weights, d_masks, d_query_mask,
+                            d_docs, d_scores, stream=None) -> None:
+        """Device-resident search_after (bm25_search_after_device): torch int32
+        [Q, T] queries, ``d_after`` None or a pair (float32 [Q] scores, int32
+        [Q] docs), float32 [Q, T] weights (or None), packed masks [M, W] (or
+        None) and int32 [Q] mask ids (or None) in, int32 / float32 [Q, k] out,
+        enqueued on ``stream``.  No validation: an after-docs entry < -1 is
+        "no cursor", a NaN cursor score leaves its row unspecified.  It may
+        synchronise ``stream`` once, as search_filtered_device."""
+        if d_queries.dim() != 2:
+            raise ValueError("d_queries must be a 2-D [Q, T] tensor")
+        Q, T = d_queries.shape
+        if d_weights is not None and (
+                tuple(d_weights.shape) != (Q, T) or not d_weights.dtype.is_floating_point
+                or d_weights.element_size() != 4):
+            raise ValueError(f"d_weights must be a float32 [{Q}, {T}] tensor")
+        W = (self.n_docs + 31) // 32
+        M = 0
+        if d_masks is not None:
+            if d_masks.dim() != 2 or d_masks.shape[1] != W or d_masks.element_size() != 4:
+                raise ValueError(f"d_masks must be a packed [M, {W}] tensor of 32-bit words")
+            M = d_masks.shape[0]
+        if d_query_mask is not None and d_query_mask.numel() != Q:
+            raise ValueError(f"d_query_mask must hold one mask id per query ({Q})")
+        a_s = a_d = None
+        if d_after is not None:
+            if not isinstance(d_after, (tuple, list)) or len(d_after) != 2:
+                raise ValueError("d_after must be None or a pair (scores [Q], docs [Q])")
+            a_s, a_d = d_after
+            if a_s is None or a_d is None:
+                raise ValueError("d_after needs both halves: (scores [Q], docs [Q])")
+            if (tuple(a_s.shape) != (Q,) or tuple(a_d.shape) != (Q,)
+                    or not a_s.dtype.is_floating_point or a_s.element_size() != 4
+                    or a_d.dtype.is_floating_point or a_d.element_size() != 4
+                    or not a_s.is_contiguous() or not a_d.is_contiguous()):
+                raise ValueError(f"d_after must be contiguous (float32 [{Q}], int32 [{Q}]) tensors")
+        k = int(k)
+        if d_docs.numel() != Q * k or d_scores.numel() != Q * k:
+            raise ValueError(f"d_docs and d_scores must hold {Q} x {k} results")
+        s = getattr(stream, "cuda_stream", stream) or 0
+        vp = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        check(lib.bm25_search_after_device(
+            self._h, vp(d_queries), vp(d_weights), Q, T, k, vp(d_masks) if M else None, M,
+            vp(d_query_mask), vp(a_s), vp(a_d), vp(d_docs), vp(d_scores), ctypes.c_void_p(s)))
+
     def score_docs_weighted(self, queries, weights, docs) -> np.ndarray:
         """score_docs under weighted query terms (bm25_score_docs_weighted,
         host arrays): out[q, c] is bit for bit the score search_weighted
@@ -694,10 +809,11 @@ class GpuIndex:
     KERNELS = {1: "flat_sample", 2: "flat_rest", 4: "flat_all", 8: "wave_sample",
                16: "wave_rest", 32: "wave_all", 64: "large_k", 128: "bound_keys",
                256: "bound_off", 512: "count_skips", 1024: "rest_split",
-               2048: "bound_pool", 4096: "filtered", 8192: "weighted"}  # (flags, not
+               2048: "bound_pool", 4096: "filtered", 8192: "weighted",
+               16384: "after"}  # (flags, not
     # kernels: 256 the tile-bound threshold was off, 512 REST counted the postings it
     # skipped, 1024 REST ran over split items, 2048 the threshold read the pooled bounds,
-    # 8192 the search was weighted)
+    # 8192 the search was weighted, 16384 it was called through search_after)
 
     def last_dispatch(self) -> dict:
         """What the last search launched (bm25_search_dispatch): the score

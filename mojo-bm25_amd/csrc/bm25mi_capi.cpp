@@ -464,9 +464,13 @@ int run_search(bm25_index* h, const int32_t* d_queries, int64_t Q, int64_t T, in
 // The filtered search's device pipeline on stream st (bm25mi_filter.hip);
 // caller holds h->mu and has set the device.  A search of the handle: the
 // workspace, its stream ordering and the large-k scratch as run_search's.
+// after: the call is bm25_search_after's (the dispatch flag kKAfter), with the
+// cursor arrays d_after_scores / d_after_docs (both null: no cursor).
 int run_filtered(bm25_index* h, const int32_t* d_queries, int64_t Q, int64_t T, int k,
                  const uint32_t* d_masks, int64_t M, const int32_t* d_query_mask, int32_t* d_docs,
-                 float* d_scores, hipStream_t st, const float* d_weights = nullptr) {
+                 float* d_scores, hipStream_t st, const float* d_weights = nullptr,
+                 bool after = false, const float* d_after_scores = nullptr,
+                 const int32_t* d_after_docs = nullptr) {
   if (Q == 0 || k == 0) return BM25_OK;
   const int rc = ensure_ws(h, Q, T, std::min<int>(k, kMaxK), st);
   if (rc) return rc;
@@ -488,9 +492,11 @@ int run_filtered(bm25_index* h, const int32_t* d_queries, int64_t Q, int64_t T, 
   EventPair* ev = next_events(h);
   if (ev) HIP_TRY(hipEventRecord(ev->a, st), "hipEventRecord");
   int64_t nd = 0;
+  if (after) h->ix.disp.kernels |= kKAfter;
   HIP_TRY(launch_search_filtered(h->ix, d_queries, Q, T, k, d_masks, M, d_query_mask, h->ws,
-                                 d_docs, d_scores, &nd, st, d_weights),
-          d_weights ? "weighted search" : "filtered search");
+                                 d_docs, d_scores, &nd, st, d_weights, d_after_scores,
+                                 d_after_docs),
+          after ? "cursor search" : d_weights ? "weighted search" : "filtered search");
   h->filtered_dense = nd;
   if (ev) {
     HIP_TRY(hipEventRecord(ev->b, st), "hipEventRecord");
@@ -995,6 +1001,87 @@ int bm25_search_weighted_device(bm25_index* h, const int32_t* d_queries, const f
   static const float none = 0.f;
   return run_filtered(h, d_queries, Q, T, k, d_masks, M, d_query_mask, d_docs, d_scores,
                       (hipStream_t)stream, d_weights ? d_weights : &none);
+}
+
+int bm25_search_after(bm25_index* h, const int32_t* queries, const float* weights, int64_t Q,
+                      int64_t T, int32_t k, const uint32_t* masks, int64_t M,
+                      const int32_t* query_mask, const float* after_scores,
+                      const int32_t* after_docs, int32_t* out_docs, float* out_scores) {
+  if (!h) return fail(BM25_EINVAL, "NULL index");
+  if (Q < 0 || T < 0 || M < 0) return fail(BM25_EINVAL, "negative query or mask shape");
+  int rc = check_k(h, k);
+  if (rc) return rc;
+  if ((after_scores != nullptr) != (after_docs != nullptr))
+    return fail(BM25_EINVAL, "after_scores and after_docs must both be given or both be NULL");
+  if (Q == 0 || k == 0) return BM25_OK;
+  if (T > 0 && !queries) return fail(BM25_EINVAL, "NULL queries");
+  if (M > 0 && !masks) return fail(BM25_EINVAL, "NULL masks");
+  if (!out_docs || !out_scores) return fail(BM25_EINVAL, "NULL output");
+  rc = check_token_ids(h->ix.n_terms, 0, queries, Q * T);
+  if (rc) return rc;
+  if (weights) {
+    rc = check_weights(queries, weights, Q, T);
+    if (rc) return rc;
+  }
+  if (query_mask)
+    for (int64_t i = 0; i < Q; ++i)
+      if (query_mask[i] < -1 || query_mask[i] >= M)
+        return fail(BM25_EINVAL, "query_mask[%lld] = %d is outside [-1, %lld)", (long long)i,
+                    query_mask[i], (long long)M);
+  if (after_docs)
+    for (int64_t i = 0; i < Q; ++i) {
+      if (after_docs[i] < BM25_AFTER_NONE)
+        return fail(BM25_EINVAL,
+                    "after_docs[%lld] = %d is below BM25_AFTER_NONE (-2): a cursor names a doc "
+                    "id >= 0, -1 (exhausted) or BM25_AFTER_NONE",
+                    (long long)i, after_docs[i]);
+      if (after_docs[i] >= 0 && std::isnan(after_scores[i]))
+        return fail(BM25_EINVAL, "after_scores[%lld] = %g is not a score (the cursor of doc %d)",
+                    (long long)i, (double)after_scores[i], after_docs[i]);
+    }
+  Enter in(h);
+  if (in.rc) return in.rc;
+  rc = ensure_io(h, Q * T, Q * (int64_t)k);
+  if (rc) return rc;
+  // the weights, masks, mask ids and cursors: staging buffers of this call's own
+  const int64_t W = (h->ix.n_docs + 31) >> 5;
+  HostCall c(h->stream);
+  float* d_w = weights ? c.alloc<float>(Q * T) : nullptr;
+  uint32_t* d_masks = M > 0 ? c.alloc<uint32_t>(M * W) : nullptr;
+  int32_t* d_qm = query_mask ? c.alloc<int32_t>(Q) : nullptr;
+  if (weights) c.upload_to(d_w, weights, Q * T);
+  c.upload_to(d_masks, masks, M * W);
+  if (query_mask) c.upload_to(d_qm, query_mask, Q);
+  const float* d_as = c.upload(after_scores, after_docs ? Q : 0);
+  const int32_t* d_ad = c.upload(after_docs, after_docs ? Q : 0);
+  c.upload_to(h->d_q, queries, Q * T);
+  if (!c.ok()) return c.finish("cursor search staging");
+  c.hold(run_filtered(h, h->d_q, Q, T, k, d_masks, M, d_qm, h->d_docs, h->d_scores, h->stream,
+                      d_w, true, d_as, d_ad));
+  c.download(out_docs, h->d_docs, Q * k);
+  c.download(out_scores, h->d_scores, Q * k);
+  return c.finish("cursor search");
+}
+
+int bm25_search_after_device(bm25_index* h, const int32_t* d_queries, const float* d_weights,
+                             int64_t Q, int64_t T, int32_t k, const uint32_t* d_masks, int64_t M,
+                             const int32_t* d_query_mask, const float* d_after_scores,
+                             const int32_t* d_after_docs, int32_t* d_docs, float* d_scores,
+                             void* stream) {
+  if (!h) return fail(BM25_EINVAL, "NULL index");
+  if (Q < 0 || T < 0 || M < 0) return fail(BM25_EINVAL, "negative query or mask shape");
+  int rc = check_k(h, k);
+  if (rc) return rc;
+  if ((d_after_scores != nullptr) != (d_after_docs != nullptr))
+    return fail(BM25_EINVAL, "after_scores and after_docs must both be given or both be NULL");
+  if (Q == 0 || k == 0) return BM25_OK;
+  if (T > 0 && !d_queries) return fail(BM25_EINVAL, "NULL queries");
+  if (M > 0 && !d_masks) return fail(BM25_EINVAL, "NULL masks");
+  if (!d_docs || !d_scores) return fail(BM25_EINVAL, "NULL output");
+  Enter in(h);
+  if (in.rc) return in.rc;
+  return run_filtered(h, d_queries, Q, T, k, d_masks, M, d_query_mask, d_docs, d_scores,
+                      (hipStream_t)stream, d_weights, true, d_after_scores, d_after_docs);
 }
 
 int bm25_search_filtered_stats(bm25_index* h, int64_t* out, int32_t n) {

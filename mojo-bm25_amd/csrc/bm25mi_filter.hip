@@ -33,6 +33,15 @@
 // posting by its term's weight before the add.  Nothing above
 // relies on a tile bound or on the values' sign, which is what weights of
 // either sign need.
+//
+// The cursor search (bm25_search_after; replaces no reference call:
+// BM25v.search has no cursor, bm25_native.py:76-158) is the same pass with one
+// more per-document predicate: a result is the total order of one u64 key, so
+// "strictly after (score, doc)" is key < ckey[q].  cursor_keys_kernel builds
+// the keys in the handle-local frame once per call; pass A's candidates are
+// then the tiles' best eligible keys, theta an eligible document's own key,
+// pass B emits eligible keys only, and the dense path clamps a row's need to
+// its eligible count (bm25mi_large.hip).
 #include "bm25mi_internal.h"
 
 namespace bm25mi {
@@ -169,6 +178,42 @@ __global__ __launch_bounds__(kFinT) void filter_finish_kernel(
   }
 }
 
+// The cursor keys of a call, in the handle-local doc frame: key (score_key(s),
+// 0xFFFFFFFF - d) is eligible iff it is < ckey[q].  after_docs[q] < -1: no
+// cursor (~0: every real key is below it); -1: the list is exhausted (0: no
+// key is below it) — and the row's copy of the query is blanked to padding, so
+// no pass reads a posting for it; otherwise the cursor (after_scores[q],
+// after_docs[q]) with the doc moved from the global frame, carrying into the
+// score field where it falls outside the frame's 32 bits (as row_kth_kernel<0>
+// of bm25mi_large.hip): a doc below doc_offset precedes every local document,
+// so the whole run of equal scores is still eligible.  One workgroup per row;
+// qcopy [Q][T] is the queries with the exhausted rows blanked.
+__global__ __launch_bounds__(64) void cursor_keys_kernel(const float* __restrict__ after_scores,
+                                                         const int32_t* __restrict__ after_docs,
+                                                         int64_t doc_offset,
+                                                         const int32_t* __restrict__ queries,
+                                                         int64_t T, uint64_t* __restrict__ ckey,
+                                                         int32_t* __restrict__ qcopy) {
+  const int64_t q = blockIdx.x;
+  const int32_t c = after_docs[q];
+  uint64_t key;
+  if (c < -1) {
+    key = ~0ull;
+  } else if (c == -1) {
+    key = 0ull;
+  } else {
+    const uint64_t hi = (uint64_t)score_key(after_scores[q]);
+    const int64_t cl = (int64_t)c - doc_offset;  // (< 2^31: c is an int32, doc_offset >= 0)
+    if (cl < 0)  // before every local document: all of the equal scores follow it
+      key = hi == 0xFFFFFFFFull ? ~0ull : (hi + 1ull) << 32;
+    else
+      key = (hi << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)cl);
+  }
+  if (threadIdx.x == 0) ckey[q] = key;
+  for (int64_t j = threadIdx.x; j < T; j += 64)
+    qcopy[q * T + j] = key == 0ull ? -1 : queries[q * T + j];
+}
+
 #define FL_TRY(expr)                    \
   do {                                  \
     const hipError_t e_ = (expr);       \
@@ -181,7 +226,8 @@ hipError_t launch_search_filtered(const DevIndex& ix, const int32_t* d_queries, 
                                   int64_t T, int k, const uint32_t* d_masks, int64_t M,
                                   const int32_t* d_query_mask, const Workspace& ws,
                                   int32_t* d_docs, float* d_scores, int64_t* n_dense,
-                                  hipStream_t st, const float* d_weights) {
+                                  hipStream_t st, const float* d_weights,
+                                  const float* d_after_scores, const int32_t* d_after_docs) {
   *n_dense = 0;
   if (Q == 0 || k == 0) return hipSuccess;
   if (k > ix.n_docs) return hipErrorInvalidValue;
@@ -189,16 +235,25 @@ hipError_t launch_search_filtered(const DevIndex& ix, const int32_t* d_queries, 
   Scratch sc(st, ws.arena);
   int32_t* census = nullptr;
   uint32_t* total = nullptr;
-  if (d_weights) {
-    ix.disp.kernels |= kKWeighted;
-    // the weighted search without masks and mask ids: no filter for every
-    // query, as mask ids of -1 (the kernels read a null d_query_mask as mask 0)
-    if (M == 0 && !d_query_mask) {
-      int32_t* none = nullptr;
-      FL_TRY(sc.get(&none, Q));
-      FL_TRY(hipMemsetAsync(none, 0xFF, sizeof(int32_t) * Q, st));
-      d_query_mask = none;
-    }
+  if ((d_after_scores != nullptr) != (d_after_docs != nullptr)) return hipErrorInvalidValue;
+  uint64_t* ckey = nullptr;
+  if (d_after_docs) {
+    int32_t* qcopy = nullptr;
+    FL_TRY(sc.get(&ckey, Q));
+    FL_TRY(sc.get(&qcopy, Q * T));
+    hipLaunchKernelGGL(cursor_keys_kernel, dim3((unsigned)Q), dim3(64), 0, st, d_after_scores,
+                       d_after_docs, ix.doc_offset, d_queries, T, ckey, qcopy);
+    d_queries = qcopy;
+  }
+  if (d_weights) ix.disp.kernels |= kKWeighted;
+  // no masks and no mask ids (the weighted and the cursor search allow it):
+  // no filter for every query, as mask ids of -1 (the kernels read a null
+  // d_query_mask as mask 0)
+  if (M == 0 && !d_query_mask) {
+    int32_t* none = nullptr;
+    FL_TRY(sc.get(&none, Q));
+    FL_TRY(hipMemsetAsync(none, 0xFF, sizeof(int32_t) * Q, st));
+    d_query_mask = none;
   }
   FL_TRY(sc.get(&census, M * ix.ntiles));
   FL_TRY(sc.get(&total, M));
@@ -210,15 +265,16 @@ hipError_t launch_search_filtered(const DevIndex& ix, const int32_t* d_queries, 
   if (!ix.opt.filter_tiles || k > kMaxK) {
     *n_dense = Q;
     return launch_search_filtered_dense(ix, d_queries, T, k, d_masks, d_query_mask, total, nullptr,
-                                        Q, d_docs, d_scores, st, ws.arena, d_weights);
+                                        Q, d_docs, d_scores, st, ws.arena, d_weights, ckey);
   }
   ix.disp.kernels |= kKFiltered;
   FL_TRY(launch_filter_pass_a(ix, d_queries, Q, T, d_masks, d_query_mask, census, ws.cand,
-                              ws.counters + 5, st, d_weights));
+                              ws.counters + 5, st, d_weights, ckey));
   hipLaunchKernelGGL(filter_theta_kernel, dim3((unsigned)Q), dim3(kFinT), 0, st, ws.cand,
                      ix.ntiles * kTileM, (uint32_t)k, ws.theta, ws.list_cnt);
   FL_TRY(launch_filter_pass_b(ix, d_queries, Q, T, d_masks, d_query_mask, ws.cand, ws.theta,
-                              ws.list, ws.list_cnt, ws.list_cap, ws.counters + 3, st, d_weights));
+                              ws.list, ws.list_cnt, ws.list_cap, ws.counters + 3, st, d_weights,
+                              ckey));
   hipLaunchKernelGGL(filter_finish_kernel, dim3((unsigned)Q), dim3(kFinT), 0, st, ws.list,
                      ws.list_cnt, ws.list_cap, (int32_t)k, ix.doc_offset, d_docs, d_scores,
                      ws.slow, ws.counters + 2);
@@ -231,7 +287,7 @@ hipError_t launch_search_filtered(const DevIndex& ix, const int32_t* d_queries, 
   *n_dense = nfb;
   if (nfb == 0) return hipSuccess;
   return launch_search_filtered_dense(ix, d_queries, T, k, d_masks, d_query_mask, total, ws.slow,
-                                      nfb, d_docs, d_scores, st, ws.arena, d_weights);
+                                      nfb, d_docs, d_scores, st, ws.arena, d_weights, ckey);
 }
 
 }  // namespace bm25mi

@@ -106,6 +106,7 @@ enum {
   kKBoundPool = 2048,  // (a flag) the tile-bound threshold came from the pooled bounds
   kKFiltered = 4096,   // the filtered search's tile passes (bm25mi_filter.hip)
   kKWeighted = 8192,   // (a flag) the search was weighted (bm25_search_weighted)
+  kKAfter = 16384,     // (a flag) the search came through bm25_search_after(_device)
 };
 struct Dispatch {
   uint32_t kernels = 0;       // kK* bits of the score kernels launched
@@ -446,30 +447,38 @@ hipError_t launch_merge_large(const int32_t* d_docs, const float* d_scores, int6
 // census is 0 (*d_skipped += those pairs); pass B: the pairs whose best key
 // is >= d_theta[q] scored again (*d_rescored += them), their allowed keys >=
 // theta appended to d_list[q][C] (d_list_cnt[q] counts past C: overflow).
+// d_ckey [Q] (or null; bm25_search_after): the cursor instantiations — only
+// keys < d_ckey[q] are candidates (pass A) and emitted (pass B); a row whose
+// key is 0 reads no posting and counts in *d_skipped.
 hipError_t launch_filter_census(const DevIndex& ix, const uint32_t* d_masks, int64_t M,
                                 int32_t* d_census, uint32_t* d_total, hipStream_t stream);
 hipError_t launch_filter_pass_a(const DevIndex& ix, const int32_t* d_queries, int64_t Q, int64_t T,
                                 const uint32_t* d_masks, const int32_t* d_query_mask,
                                 const int32_t* d_census, uint64_t* d_cand, int32_t* d_skipped,
-                                hipStream_t stream, const float* d_weights = nullptr);
+                                hipStream_t stream, const float* d_weights = nullptr,
+                                const uint64_t* d_ckey = nullptr);
 hipError_t launch_filter_pass_b(const DevIndex& ix, const int32_t* d_queries, int64_t Q, int64_t T,
                                 const uint32_t* d_masks, const int32_t* d_query_mask,
                                 const uint64_t* d_cand, const uint64_t* d_theta, uint64_t* d_list,
                                 int32_t* d_list_cnt, int32_t C, int32_t* d_rescored,
-                                hipStream_t stream, const float* d_weights = nullptr);
+                                hipStream_t stream, const float* d_weights = nullptr,
+                                const uint64_t* d_ckey = nullptr);
 // The dense path (bm25mi_large.hip), exact for every k, index and mask: per
 // chunk of queries the dense scores, the radix selection with the mask
 // applied where keys are formed and k_q = min(k, allowed documents of the
 // query's mask) (d_total, as launch_filter_census wrote it), the row sort and
 // the padded write.  d_ids (or null) names the nq rows of the batch to serve
 // (a device array): their queries are gathered and their results scattered
-// into d_docs / d_scores [Q][k]; otherwise nq = Q rows in order.
+// into d_docs / d_scores [Q][k]; otherwise nq = Q rows in order.  d_ckey [Q]
+// (or null): the batch's cursor keys, gathered with the rows; k_q is then
+// clamped to the row's eligible keys by the selection's first digit pass.
 hipError_t launch_search_filtered_dense(const DevIndex& ix, const int32_t* d_queries, int64_t T,
                                         int k, const uint32_t* d_masks,
                                         const int32_t* d_query_mask, const uint32_t* d_total,
                                         const int32_t* d_ids, int64_t nq, int32_t* d_docs,
                                         float* d_scores, hipStream_t stream, LargeArena* arena,
-                                        const float* d_weights = nullptr);
+                                        const float* d_weights = nullptr,
+                                        const uint64_t* d_ckey = nullptr);
 // The whole filtered search (bm25mi_filter.hip): the census, then the tile
 // passes (k <= kMaxK and the filter_tiles option), theta, the lists' sort and
 // padded write, and the dense path for the queries whose list overflowed —
@@ -478,11 +487,18 @@ hipError_t launch_search_filtered_dense(const DevIndex& ix, const int32_t* d_que
 // min(k, kMaxK)); counters [2] / [5] / [3] = queries handed to the dense path
 // by the tile passes / pairs pass A skipped / pairs pass B re-scored.
 // *n_dense: queries the dense path served.
+// d_after_scores / d_after_docs [Q] (both or neither; bm25_search_after): row
+// q returns the documents strictly after the cursor (score, global doc id) in
+// the result order; d_after_docs[q] < -1: no cursor, -1: an exhausted list
+// (all padding, no posting read).  Then M == 0 with a null d_query_mask means
+// no filter for every query, as with weights.
 hipError_t launch_search_filtered(const DevIndex& ix, const int32_t* d_queries, int64_t Q,
                                   int64_t T, int k, const uint32_t* d_masks, int64_t M,
                                   const int32_t* d_query_mask, const Workspace& ws,
                                   int32_t* d_docs, float* d_scores, int64_t* n_dense,
-                                  hipStream_t stream, const float* d_weights = nullptr);
+                                  hipStream_t stream, const float* d_weights = nullptr,
+                                  const float* d_after_scores = nullptr,
+                                  const int32_t* d_after_docs = nullptr);
 
 // Boolean term filters as allow-masks (bm25mi_termmask.hip): d_out[M][W] in
 // the layout above, row m = the documents d < n_docs that d_base allows

@@ -4259,11 +4259,15 @@ __device__ __forceinline__ int32_t filter_mask_of(const FilterArgs& f, int64_t q
 // into cand[q][tile][kTileM] (handle-local doc ids; key 0: none).  A tile
 // whose census is 0 reads no posting.  Disallowed entries get the score bits
 // 0xFFFFFFFF, whose key is 0 (select_top's empty slot).
-template <int S, bool WT = false>
+// CUR (bm25_search_after): an entry whose key is >= ckey[q] — at or before the
+// row's cursor — is treated as disallowed, so the candidates are the tile's
+// best eligible keys; a row whose ckey is 0 (an exhausted list) skips the tile
+// as a zero census does and counts in `skipped` with it.
+template <int S, bool WT = false, bool CUR = false>
 __global__ __launch_bounds__(64 * kWaves) void filter_pass_a_kernel(
     IndexArgs a, const int32_t* __restrict__ queries, int32_t T, int64_t nq, FilterArgs f,
     uint64_t* __restrict__ cand, int32_t* __restrict__ skipped,
-    const float* __restrict__ weights) {
+    const float* __restrict__ weights, const uint64_t* __restrict__ ckey) {
   constexpr int D = 1 << S;
   __shared__ __attribute__((aligned(16))) float acc_all[kWaves * D];
   const int wave = uniform((int)(threadIdx.x >> 6));
@@ -4284,16 +4288,31 @@ __global__ __launch_bounds__(64 * kWaves) void filter_pass_a_kernel(
     const int64_t tile = xcd + 8 * tl;
     const int32_t m = filter_mask_of(f, q);
     uint64_t* out = cand + (q * a.ntiles + tile) * kTileM;
-    if (m >= 0 && f.census[(int64_t)m * a.ntiles + tile] == 0) {  // wave-uniform
+    uint64_t ck = ~0ull;
+    if constexpr (CUR) ck = ckey[q];  // (wave-uniform, as theta[q] of pass B)
+    if ((m >= 0 && f.census[(int64_t)m * a.ntiles + tile] == 0) ||
+        (CUR && ck == 0ull)) {  // wave-uniform
       if (lane_id() < kTileM) out[lane_id()] = 0ull;
       ++nskip;
       continue;
     }
-    const uint64_t allow = lane_allow<S>(m >= 0 ? f.masks + (int64_t)m * f.W : nullptr, f.W, tile,
-                                         a.n_docs);
+    uint64_t allow = lane_allow<S>(m >= 0 ? f.masks + (int64_t)m * f.W : nullptr, f.W, tile,
+                                   a.n_docs);
     add_item<S, WT>(a, tile, queries + q * T, T, acc, WT ? weights + q * T : nullptr);
     float fv[D / 64];
     take_entries<S>(acc, fv);
+    // the entries after the cursor, as bits of the allow word: 32 compares and
+    // selects, no branch (an if per entry compiled to a store-less branch for
+    // entry 0 with this toolchain; tests/test_gpu_search_after.py pages over
+    // documents 0, 4, 8, ... to hold it)
+    if constexpr (CUR) {
+      const uint32_t base = (uint32_t)(tile << S);
+      uint64_t after = 0;
+#pragma unroll
+      for (int e = 0; e < D / 64; ++e)
+        after |= (uint64_t)(make_key(fv[e], base + entry_doc(e, lane_id())) < ck) << e;
+      allow &= after;
+    }
 #pragma unroll
     for (int e = 0; e < D / 64; ++e)
       if (!((allow >> e) & 1u)) fv[e] = __uint_as_float(0xFFFFFFFFu);
@@ -4307,12 +4326,15 @@ __global__ __launch_bounds__(64 * kWaves) void filter_pass_a_kernel(
 // (one atomic per wave; a list past its capacity C only counts, as
 // emit_above's).  No other tile holds such a key.  A wave looks at 64 pairs
 // at a time (query-major: the 64 keys it tests are near each other).
-template <int S, bool WT = false>
+// CUR: only the keys below ckey[q] (after the row's cursor) are emitted — the
+// counting loop and the store loop share one predicate (emit_key).
+template <int S, bool WT = false, bool CUR = false>
 __global__ __launch_bounds__(64 * kWaves) void filter_pass_b_kernel(
     IndexArgs a, const int32_t* __restrict__ queries, int32_t T, int64_t nq, FilterArgs f,
     const uint64_t* __restrict__ cand, const uint64_t* __restrict__ theta,
     uint64_t* __restrict__ list, int32_t* __restrict__ list_cnt, int32_t C,
-    int32_t* __restrict__ rescored, const float* __restrict__ weights) {
+    int32_t* __restrict__ rescored, const float* __restrict__ weights,
+    const uint64_t* __restrict__ ckey) {
   constexpr int D = 1 << S;
   constexpr int E = D / 64;
   __shared__ __attribute__((aligned(16))) float acc_all[kWaves * D];
@@ -4338,6 +4360,9 @@ __global__ __launch_bounds__(64 * kWaves) void filter_pass_b_kernel(
       const int64_t q = it / a.ntiles, tile = it - q * a.ntiles;
       const int32_t m = filter_mask_of(f, q);
       const uint64_t th = theta[q];
+      uint64_t ck = ~0ull;
+      if constexpr (CUR) ck = ckey[q];  // (wave-uniform, as th)
+      auto emit_key = [&](uint64_t key) { return key >= th && (!CUR || key < ck); };
       const uint64_t allow = lane_allow<S>(m >= 0 ? f.masks + (int64_t)m * f.W : nullptr, f.W,
                                            tile, a.n_docs);
       add_item<S, WT>(a, tile, queries + q * T, T, acc, WT ? weights + q * T : nullptr);
@@ -4348,7 +4373,7 @@ __global__ __launch_bounds__(64 * kWaves) void filter_pass_b_kernel(
 #pragma unroll
       for (int e = 0; e < E; ++e) {
         const uint64_t key = make_key(fv[e], (uint32_t)(base + entry_doc(e, lane)));
-        c += (int)((allow >> e) & 1u) & (int)(key >= th);
+        c += (int)((allow >> e) & 1u) & (int)emit_key(key);
       }
       ++nres;
       if (__ballot(c > 0) == 0ull) continue;
@@ -4360,7 +4385,7 @@ __global__ __launch_bounds__(64 * kWaves) void filter_pass_b_kernel(
 #pragma unroll
       for (int e = 0; e < E; ++e) {
         const uint64_t key = make_key(fv[e], (uint32_t)(base + entry_doc(e, lane)));
-        if (((allow >> e) & 1u) && key >= th) {
+        if (((allow >> e) & 1u) && emit_key(key)) {
           if (pos < C) lq[pos] = key;
           ++pos;
         }
@@ -4388,25 +4413,39 @@ static FilterArgs filter_args(const DevIndex& ix, const uint32_t* d_masks,
 hipError_t launch_filter_pass_a(const DevIndex& ix, const int32_t* d_queries, int64_t Q, int64_t T,
                                 const uint32_t* d_masks, const int32_t* d_query_mask,
                                 const int32_t* d_census, uint64_t* d_cand, int32_t* d_skipped,
-                                hipStream_t stream, const float* d_weights) {
+                                hipStream_t stream, const float* d_weights,
+                                const uint64_t* d_ckey) {
   if (Q == 0 || ix.ntiles == 0) return hipSuccess;
   if (ix.tile_shift != BM25_TILE_SHIFT) return hipErrorInvalidValue;
   constexpr int S = BM25_TILE_SHIFT;
   // (a multiple of 8: one share of the workgroups per XCD)
   const int64_t need = ((Q * ix.ntiles + 8 * kWaves - 1) / (8 * kWaves)) * 8;
   const FilterArgs f = filter_args(ix, d_masks, d_query_mask, d_census);
+  if (d_ckey) {  // the cursor instantiations (bm25_search_after), weighted or not
+    auto go = [&](auto kern) {
+      const int grid = (int)std::min<int64_t>(need, persistent_grid(kern, 64 * kWaves));
+      hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * kWaves), 0, stream, args_of(ix),
+                         d_queries, (int32_t)T, Q, f, d_cand, d_skipped, d_weights, d_ckey);
+    };
+    if (d_weights)
+      go(filter_pass_a_kernel<S, true, true>);
+    else
+      go(filter_pass_a_kernel<S, false, true>);
+    return hipGetLastError();
+  }
   if (d_weights) {
     const int grid = (int)std::min<int64_t>(
         need, persistent_grid(filter_pass_a_kernel<S, true>, 64 * kWaves));
     hipLaunchKernelGGL((filter_pass_a_kernel<S, true>), dim3((unsigned)grid), dim3(64 * kWaves), 0,
                        stream, args_of(ix), d_queries, (int32_t)T, Q, f, d_cand, d_skipped,
-                       d_weights);
+                       d_weights, d_ckey);
     return hipGetLastError();
   }
   const int grid =
       (int)std::min<int64_t>(need, persistent_grid(filter_pass_a_kernel<S>, 64 * kWaves));
   hipLaunchKernelGGL((filter_pass_a_kernel<S>), dim3((unsigned)grid), dim3(64 * kWaves), 0, stream,
-                     args_of(ix), d_queries, (int32_t)T, Q, f, d_cand, d_skipped, d_weights);
+                     args_of(ix), d_queries, (int32_t)T, Q, f, d_cand, d_skipped, d_weights,
+                     d_ckey);
   return hipGetLastError();
 }
 
@@ -4414,25 +4453,39 @@ hipError_t launch_filter_pass_b(const DevIndex& ix, const int32_t* d_queries, in
                                 const uint32_t* d_masks, const int32_t* d_query_mask,
                                 const uint64_t* d_cand, const uint64_t* d_theta, uint64_t* d_list,
                                 int32_t* d_list_cnt, int32_t C, int32_t* d_rescored,
-                                hipStream_t stream, const float* d_weights) {
+                                hipStream_t stream, const float* d_weights,
+                                const uint64_t* d_ckey) {
   if (Q == 0 || ix.ntiles == 0) return hipSuccess;
   if (ix.tile_shift != BM25_TILE_SHIFT) return hipErrorInvalidValue;
   constexpr int S = BM25_TILE_SHIFT;
   const int64_t need = (Q * ix.ntiles + 64 * kWaves - 1) / (64 * kWaves);
   const FilterArgs f = filter_args(ix, d_masks, d_query_mask, nullptr);
+  if (d_ckey) {  // (as launch_filter_pass_a)
+    auto go = [&](auto kern) {
+      const int grid = (int)std::min<int64_t>(need, persistent_grid(kern, 64 * kWaves));
+      hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * kWaves), 0, stream, args_of(ix),
+                         d_queries, (int32_t)T, Q, f, d_cand, d_theta, d_list, d_list_cnt, C,
+                         d_rescored, d_weights, d_ckey);
+    };
+    if (d_weights)
+      go(filter_pass_b_kernel<S, true, true>);
+    else
+      go(filter_pass_b_kernel<S, false, true>);
+    return hipGetLastError();
+  }
   if (d_weights) {
     const int grid = (int)std::min<int64_t>(
         need, persistent_grid(filter_pass_b_kernel<S, true>, 64 * kWaves));
     hipLaunchKernelGGL((filter_pass_b_kernel<S, true>), dim3((unsigned)grid), dim3(64 * kWaves), 0,
                        stream, args_of(ix), d_queries, (int32_t)T, Q, f, d_cand, d_theta, d_list,
-                       d_list_cnt, C, d_rescored, d_weights);
+                       d_list_cnt, C, d_rescored, d_weights, d_ckey);
     return hipGetLastError();
   }
   const int grid =
       (int)std::min<int64_t>(need, persistent_grid(filter_pass_b_kernel<S>, 64 * kWaves));
   hipLaunchKernelGGL((filter_pass_b_kernel<S>), dim3((unsigned)grid), dim3(64 * kWaves), 0, stream,
                      args_of(ix), d_queries, (int32_t)T, Q, f, d_cand, d_theta, d_list, d_list_cnt,
-                     C, d_rescored, d_weights);
+                     C, d_rescored, d_weights, d_ckey);
   return hipGetLastError();
 }
 

@@ -73,6 +73,9 @@ struct MaskArgs {
   const int32_t* qm = nullptr;
   const uint32_t* total = nullptr;
   int64_t W = 0;
+  // the cursor keys of the chunk's rows (CUR instantiations, bm25_search_after):
+  // a key is eligible iff it is < ckey[g]
+  const uint64_t* ckey = nullptr;
 };
 __device__ __forceinline__ const uint32_t* mask_row(const MaskArgs& ma, int64_t g) {
   const int32_t m = ma.qm ? ma.qm[g] : 0;
@@ -100,7 +103,8 @@ __global__ __launch_bounds__(64) void lk_init_kernel(SelState* __restrict__ st, 
 // (shift + 8) equal its prefix.  Exact zero sums (untouched documents, most
 // of a row) share one digit while shift >= 32 (their doc bits lie below it):
 // they are counted in a register, not with same-address LDS atomics.
-template <bool MASKED>
+// CUR: only the keys below the row's cursor key count (block-uniform load).
+template <bool MASKED, bool CUR = false>
 __global__ __launch_bounds__(256) void lk_hist_kernel(const float* __restrict__ scores,
                                                       int64_t stride, int64_t n_docs, int shift,
                                                       const SelState* __restrict__ st,
@@ -122,6 +126,8 @@ __global__ __launch_bounds__(256) void lk_hist_kernel(const float* __restrict__ 
   const int64_t n4 = (n_docs + 3) >> 2;
   const uint32_t* mrow = nullptr;
   if constexpr (MASKED) mrow = mask_row(ma, g);
+  uint64_t ck = ~0ull;
+  if constexpr (CUR) ck = ma.ckey[g];
   uint32_t zeros = 0;
   const uint32_t lane = threadIdx.x & 63u;
   // every lane of a wave runs the same rounds (the ballots below)
@@ -145,11 +151,12 @@ __global__ __launch_bounds__(256) void lk_hist_kernel(const float* __restrict__ 
       const int64_t d = 4 * i + c;
       bool pend = d < n_docs;
       if constexpr (MASKED) pend = pend && ((mbits >> c) & 1u);
+      const uint64_t key = doc_key(fe[c], (uint32_t)d);
+      if constexpr (CUR) pend = pend && key < ck;
       if (pend && zfast && __float_as_uint(fe[c]) == 0u) {
         zeros += zmatch ? 1u : 0u;
         pend = false;
       }
-      const uint64_t key = doc_key(fe[c], (uint32_t)d);
       pend = pend && match(key);
       const uint32_t dig = (uint32_t)(key >> shift) & 255u;
       // the high digits of a row's scores are few (one exponent range): the
@@ -179,6 +186,11 @@ __global__ __launch_bounds__(256) void lk_hist_kernel(const float* __restrict__ 
 // The digit of the pass that holds each query's k-th key (one wave per
 // query): bins scanned from the top; the histogram row is cleared for the
 // next pass.
+// CLAMP (the cursor search, whose eligible documents no census counts): the
+// first pass's histogram (shift 56: every eligible key matches) sums to the
+// row's eligible keys; a row with fewer than it needs takes all of them —
+// decided at once with the k-th key 0, the rest of its row stays padding.
+template <bool CLAMP = false>
 __global__ __launch_bounds__(64) void lk_pick_kernel(SelState* __restrict__ st,
                                                      uint32_t* __restrict__ hist, int shift) {
   const int64_t g = blockIdx.x;
@@ -195,6 +207,12 @@ __global__ __launch_bounds__(64) void lk_pick_kernel(SelState* __restrict__ st,
   const uint32_t t = c[0] + c[1] + c[2] + c[3];
   const uint32_t incl = wave_scan(t);
   const uint32_t tot = __shfl((int)incl, 63, 64);
+  if constexpr (CLAMP) {
+    if (shift == 56 && tot < s.need) {  // wave-uniform
+      if (lane == 0) st[g] = SelState{0ull, tot, 1u};
+      return;
+    }
+  }
   uint32_t above = tot - incl;  // keys in the bins of the higher lanes
 #pragma unroll
   for (int j = 3; j >= 0; --j) {
@@ -219,7 +237,7 @@ __global__ __launch_bounds__(64) void lk_pick_kernel(SelState* __restrict__ st,
 // the stage's capacity (a zero-fill row's keys crowd into its first docs) take
 // the global atomic directly.
 constexpr int kCompactStage = 2048;
-template <bool MASKED>
+template <bool MASKED, bool CUR = false>
 __global__ __launch_bounds__(256) void lk_compact_kernel(const float* __restrict__ scores,
                                                          int64_t stride, int64_t n_docs,
                                                          const SelState* __restrict__ st,
@@ -237,6 +255,8 @@ __global__ __launch_bounds__(256) void lk_compact_kernel(const float* __restrict
   const int64_t n4 = (n_docs + 3) >> 2;
   const uint32_t* mrow = nullptr;
   if constexpr (MASKED) mrow = mask_row(ma, g);
+  uint64_t ck = ~0ull;
+  if constexpr (CUR) ck = ma.ckey[g];
   // every lane of a wave runs the same rounds (ballots below)
   const int64_t step = (int64_t)gridDim.x * 256;
   const int64_t rounds = (n4 + step - 1) / step;
@@ -258,7 +278,7 @@ __global__ __launch_bounds__(256) void lk_compact_kernel(const float* __restrict
       const int64_t d = 4 * i + c;
       uint64_t key = d < n_docs ? doc_key(fe[c], (uint32_t)d) : 0ull;
       if constexpr (MASKED) key = ((mbits >> c) & 1u) ? key : 0ull;
-      const bool keep = key != 0ull && key >= kth;
+      const bool keep = key != 0ull && key >= kth && (!CUR || key < ck);
       const uint64_t m = __ballot(keep);
       if (m == 0ull) continue;
       int p0 = 0;
@@ -508,7 +528,8 @@ hipError_t launch_search_large(const DevIndex& ix, const int32_t* d_queries, int
     for (int shift = 56; shift >= 0; shift -= 8) {
       hipLaunchKernelGGL(lk_hist_kernel<false>, grid, dim3(256), 0, st, scores, Np, ix.n_docs,
                          shift, state, hist, MaskArgs{});
-      hipLaunchKernelGGL(lk_pick_kernel, dim3((unsigned)g), dim3(64), 0, st, state, hist, shift);
+      hipLaunchKernelGGL(lk_pick_kernel<false>, dim3((unsigned)g), dim3(64), 0, st, state, hist,
+                         shift);
     }
     hipLaunchKernelGGL(lk_compact_kernel<false>, grid, dim3(256), 0, st, scores, Np, ix.n_docs,
                        state, cnt, keys, (int64_t)kv, MaskArgs{});
@@ -934,12 +955,15 @@ hipError_t launch_search_large_lists(const DevIndex& ix, const int32_t* d_querie
 // The filtered search's dense path: launch_search_large's sequence with the
 // mask applied where keys are formed and a per-row k_q; a row's unused key
 // slots stay 0 (cleared per chunk) and sort last, written as padding.
+// d_ckey (bm25_search_after): the cursor instantiations — the cursor applied
+// where keys are formed, and the row's need clamped to its eligible keys by
+// the first digit pass (lk_pick_kernel<true>).
 hipError_t launch_search_filtered_dense(const DevIndex& ix, const int32_t* d_queries, int64_t T,
                                         int k, const uint32_t* d_masks,
                                         const int32_t* d_query_mask, const uint32_t* d_total,
                                         const int32_t* d_ids, int64_t nq, int32_t* d_docs,
                                         float* d_scores, hipStream_t st, LargeArena* arena,
-                                        const float* d_weights) {
+                                        const float* d_weights, const uint64_t* d_ckey) {
   if (nq == 0 || k == 0) return hipSuccess;
   if (k > ix.n_docs) return hipErrorInvalidValue;
   ix.disp.kernels |= kKLarge;
@@ -950,6 +974,7 @@ hipError_t launch_search_filtered_dense(const DevIndex& ix, const int32_t* d_que
   const int32_t* q = d_queries;
   const int32_t* qm = d_query_mask;
   const float* wq = d_weights;
+  const uint64_t* ckq = d_ckey;
   int32_t* od = d_docs;
   float* os = d_scores;
   if (d_ids) {
@@ -974,6 +999,13 @@ hipError_t launch_search_filtered_dense(const DevIndex& ix, const int32_t* d_que
       hipLaunchKernelGGL(gather_rows_kernel, dim3(grid_for(nq, 256, 4096)), dim3(256), 0, st,
                          d_query_mask, d_ids, nq, (int64_t)1, fm);
       qm = fm;
+    }
+    if (d_ckey) {  // the cursor keys: rows of two 4-byte elements
+      int32_t* fc = nullptr;
+      LK_TRY(sc.get(&fc, nq * 2));
+      hipLaunchKernelGGL(gather_rows_kernel, dim3(grid_for(nq * 2, 256, 4096)), dim3(256), 0, st,
+                         reinterpret_cast<const int32_t*>(d_ckey), d_ids, nq, (int64_t)2, fc);
+      ckq = reinterpret_cast<const uint64_t*>(fc);
     }
   }
   const int64_t per_q = Np * 4 + (int64_t)k * 16 + 256 * 4 + 64 + sort_bytes(1, k);
@@ -1004,18 +1036,31 @@ hipError_t launch_search_filtered_dense(const DevIndex& ix, const int32_t* d_que
   for (int64_t q0 = 0; q0 < nq; q0 += G) {
     const int64_t g = std::min<int64_t>(G, nq - q0);
     ma.qm = qm ? qm + q0 : nullptr;
+    ma.ckey = ckq ? ckq + q0 : nullptr;
     LK_TRY(launch_scores_batch(ix, q + q0 * T, g, T, Np, scores, st, wq ? wq + q0 * T : nullptr));
     LK_TRY(hipMemsetAsync(keys, 0, sizeof(uint64_t) * g * k, st));
     hipLaunchKernelGGL(lk_init_kernel<true>, dim3(1), dim3(64), 0, st, state, g, (uint32_t)k, cnt,
                        ma);
     const dim3 grid(grid_for(n4, 256 * 8, 1024), (unsigned)g);
     for (int shift = 56; shift >= 0; shift -= 8) {
-      hipLaunchKernelGGL(lk_hist_kernel<true>, grid, dim3(256), 0, st, scores, Np, ix.n_docs,
-                         shift, state, hist, ma);
-      hipLaunchKernelGGL(lk_pick_kernel, dim3((unsigned)g), dim3(64), 0, st, state, hist, shift);
+      if (ckq) {
+        hipLaunchKernelGGL((lk_hist_kernel<true, true>), grid, dim3(256), 0, st, scores, Np,
+                           ix.n_docs, shift, state, hist, ma);
+        hipLaunchKernelGGL(lk_pick_kernel<true>, dim3((unsigned)g), dim3(64), 0, st, state, hist,
+                           shift);
+      } else {
+        hipLaunchKernelGGL(lk_hist_kernel<true>, grid, dim3(256), 0, st, scores, Np, ix.n_docs,
+                           shift, state, hist, ma);
+        hipLaunchKernelGGL(lk_pick_kernel<false>, dim3((unsigned)g), dim3(64), 0, st, state, hist,
+                           shift);
+      }
     }
-    hipLaunchKernelGGL(lk_compact_kernel<true>, grid, dim3(256), 0, st, scores, Np, ix.n_docs,
-                       state, cnt, keys, (int64_t)k, ma);
+    if (ckq)
+      hipLaunchKernelGGL((lk_compact_kernel<true, true>), grid, dim3(256), 0, st, scores, Np,
+                         ix.n_docs, state, cnt, keys, (int64_t)k, ma);
+    else
+      hipLaunchKernelGGL(lk_compact_kernel<true>, grid, dim3(256), 0, st, scores, Np, ix.n_docs,
+                         state, cnt, keys, (int64_t)k, ma);
     if (!lds_sort_write(keys, g, k, k, ix.doc_offset, od + q0 * k, os + q0 * k, st)) {
       const uint64_t* sorted = nullptr;
       LK_TRY(sort_rows(keys, alt, g, k, tmp, &sorted, st));
