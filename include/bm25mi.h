@@ -642,6 +642,12 @@ int bm25_search_finish_streams_device(bm25_index* idx, const int32_t* d_queries,
  * the reference is single-device (main.py:205).
  */
 int bm25_index_bounds_export(bm25_index* idx, uint16_t* d_out, int64_t stride, void* stream);
+/* Diagnostics: the sub-block presence masks beside the tile bounds,
+ * [n_terms][stride] u32 with the stride rules of bm25_index_bounds_export —
+ * bit s of (term, tile): the term has a posting in the tile's s-th sub-block
+ * of tile_docs / 32 documents.  EINVAL where the index keeps none (no tile
+ * bounds, BM25_TILE_MASK=0 at create, or no memory for the table). */
+int bm25_index_masks_export(bm25_index* idx, uint32_t* d_out, int64_t stride, void* stream);
 int bm25_index_set_world_bounds(bm25_index* idx, const uint16_t* d_world, int32_t world,
                                 int64_t stride, int64_t world_tiles);
 int bm25_search_shard_device(bm25_index* idx, const int32_t* d_queries, int64_t Q, int64_t T,
@@ -724,8 +730,8 @@ int bm25_search_counters(bm25_index* idx, int64_t* out, int32_t n);
  * environment (BM25_FLAT, BM25_FLAT_BW, BM25_ITEMS_PER_WAVE, BM25_SAMPLE_P,
  * BM25_LIST_CAP, BM25_CLAIM_CH, BM25_CLAIM_M, BM25_TILE_BOUND, BM25_THETA_BOUND,
  * BM25_GRID_PCT, BM25_LARGE_LISTS, BM25_COUNT_SKIPS, BM25_REST_SPLIT,
- * BM25_BOUND_POOL, BM25_FILTER_TILES, BM25_BOOL_CHUNK) at
- * bm25_index_create; these
+ * BM25_BOUND_POOL, BM25_FILTER_TILES, BM25_BOOL_CHUNK) and, for "tile_mask",
+ * from BM25_TILE_MASK, at bm25_index_create; these
  * calls change or read them afterwards, effective from the next search.
  * Results never depend on them (every setting is bit-exact); they choose
  * kernels and geometry:
@@ -781,6 +787,12 @@ int bm25_search_counters(bm25_index* idx, int64_t* out, int32_t n);
  *   "bool_chunk"     bm25_search_boolean: queries per chunk of device-built
  *                    masks (env BM25_BOOL_CHUNK); 0 (default) = automatic: at
  *                    most 1 GiB of mask words per chunk, at least one query
+ *   "tile_mask"      1 (default): the REST pass's tile bound is refined by the
+ *                    sub-block presence masks (a u32 per (term, tile) beside
+ *                    the tile bounds: bm25_index_masks_export); 0: the
+ *                    whole-tile bound alone.  Read at bm25_index_create too:
+ *                    a handle created under BM25_TILE_MASK=0 keeps no mask
+ *                    table, and the option then changes nothing
  *   "grid_pct"      percent of the device's resident workgroup slots the
  *                    persistent score kernels launch (1..100, default 100):
  *                    below 100 leaves slots for kernels of another stream
@@ -808,7 +820,9 @@ int bm25_index_get_option(const bm25_index* idx, const char* name, int64_t* valu
  *                8192 (a flag): the last search was weighted
  *                (bm25_search_weighted; it sets 4096 and / or 64 as well);
  *                16384 (a flag): the last search was called through
- *                bm25_search_after(_device), whatever its cursors
+ *                bm25_search_after(_device), whatever its cursors;
+ *                32768: tile_skip_kernel, the tile bounds' pre-pass of a flat
+ *                REST launch
  *   *term_lanes  flat kernel: term lanes per tile (8, 16, 32 or 64)
  *   band_tiles   [3]: flat kernel tiles per item of ALL, SAMPLE, REST
  *   *sample_p    sampling stride of the search (1: exact pass, 0: tile-bound

@@ -273,6 +273,15 @@ class GpuIndex:
         check(lib.bm25_index_bounds_export(self._h, ctypes.c_void_p(d_out.data_ptr()), int(stride),
                                            ctypes.c_void_p(s)))
 
+    def masks_export(self, d_out, stride: int, stream=None) -> None:
+        """This index's sub-block presence masks into d_out (a torch int32
+        [n_terms, stride] device tensor, stride as bounds_stride();
+        bm25_index_masks_export).  Bit s of (term, tile): the term has a
+        posting in the tile's s-th sub-block of tile_docs / 32 documents."""
+        s = getattr(stream, "cuda_stream", stream) or 0
+        check(lib.bm25_index_masks_export(self._h, ctypes.c_void_p(d_out.data_ptr()), int(stride),
+                                          ctypes.c_void_p(s)))
+
     def set_world_bounds(self, d_world, world: int, stride: int, world_tiles: int) -> None:
         """Every shard's tile bounds ([world, n_terms, stride] int16 on this
         device, kept referenced here) for bm25_search_shard_device; None clears."""
@@ -826,6 +835,9 @@ class GpuIndex:
         check(lib.bm25_search_dispatch(self._h, ctypes.byref(km), ctypes.byref(tl), bt,
                                        ctypes.byref(sp_)))
         return {"kernels": {n for b, n in self.KERNELS.items() if km.value & b},
+                # tile_skip_kernel ran ahead of REST (bit 32768): reported beside the
+                # set, whose exact contents callers compare against the phases taken
+                "tile_skip": bool(km.value & 32768),
                 "term_lanes": tl.value,
                 "band_tiles": {"all": bt[0], "sample": bt[1], "rest": bt[2]},
                 "sample_p": sp_.value}

@@ -112,6 +112,8 @@ struct bm25_index {
 static const OptDesc* find_opt(const char* name) {
   for (const OptDesc& d : kOpts)
     if (!strcmp(d.name, name)) return &d;
+  for (const OptDesc& d : kOptsMore)
+    if (!strcmp(d.name, name)) return &d;
   fail(BM25_EINVAL, "unknown option '%s'", name);
   return nullptr;
 }
@@ -158,6 +160,7 @@ void free_ws(Workspace& ws) {
   hipFree(ws.sub);
   hipFree(ws.sub_ipb);
   hipFree(ws.sub_done);
+  hipFree(ws.tskip);
   ws = Workspace{};
 }
 
@@ -172,13 +175,15 @@ int32_t list_cap_for(const SearchOpts& o, int64_t k) {
 // Options of a new handle: the BM25_* environment (include/bm25mi.h).
 SearchOpts env_opts() {
   SearchOpts o;
-  for (const OptDesc& d : kOpts) {
+  auto read = [&o](const OptDesc& d) {
     int v = env_int(d.env, o.*d.field);
     if (d.kind == kOptBool) v = v != 0;
     if (d.env_clamp >= 1) v = std::max(d.lo, v);
     if (d.env_clamp >= 2) v = std::min(d.hi, v);
     o.*d.field = v;
-  }
+  };
+  for (const OptDesc& d : kOpts) read(d);
+  for (const OptDesc& d : kOptsMore) read(d);
   return o;
 }
 
@@ -230,6 +235,9 @@ int ensure_ws(bm25_index* h, int64_t Q, int64_t T, int k, hipStream_t st) {
   HIP_TRY(hipMalloc(&ws.sub_ipb, sizeof(int32_t)), "hipMalloc(sub_ipb)");
   HIP_TRY(hipMalloc(&ws.sub_done, sizeof(int32_t)), "hipMalloc(sub_done)");
   HIP_TRY(hipMemsetAsync(ws.sub_done, 0, sizeof(int32_t), st), "hipMemsetAsync(sub_done)");
+  // the REST pass's tile-skip bits (tile_skip_kernel writes them per search)
+  if (h->ix.bmax)
+    HIP_TRY(hipMalloc(&ws.tskip, (size_t)std::max<int64_t>(q * tskip_stride(nt), 4)), "hipMalloc(tskip)");
   ws.cap_seg = need_seg;
   if (ws.cap_seg > 0) HIP_TRY(hipMalloc(&ws.seg, sizeof(uint64_t) * ws.cap_seg), "hipMalloc(seg)");
   ws.list_cap = C;
@@ -643,7 +651,7 @@ int bm25_index_create(int device, int64_t n_docs, int64_t n_terms, int64_t nnz,
     h->arrays = std::make_shared<IndexArrays>();
     h->arrays->device = device;
     h->arrays->p = {ix.indptr, ix.rel, ix.tl_ptr, ix.tl_tile, ix.tl_start, ix.ldoc, ix.val, ix.bmax,
-                    ix.bpool};
+                    ix.bpool, ix.tmask};
     *out = h;
   } else {
     bm25_index_destroy(h);
@@ -741,6 +749,15 @@ static int build_index(bm25_index* h, const std::vector<int64_t>& ip, const int3
         (void)hipGetLastError();
         ix.bpool = nullptr;
       }
+      // the sub-block presence masks that refine the tile bound (optional too)
+      if (c.ok() && ix.opt.tile_mask &&
+          hipMalloc(&ix.tmask, sizeof(uint32_t) * n_terms * bmax_stride(ntiles)) == hipSuccess) {
+        c.run(launch_build_tmask(ix, h->stream), "build_tmask launch");
+        h->device_bytes += (int64_t)(sizeof(uint32_t) * n_terms * bmax_stride(ntiles));
+      } else {
+        (void)hipGetLastError();
+        ix.tmask = nullptr;
+      }
     } else {
       (void)hipGetLastError();
       ix.bmax = nullptr;
@@ -784,7 +801,8 @@ int bm25_index_destroy(bm25_index* h) {
   } else {              // a create that failed part-way
     for (void* x : {(void*)h->ix.indptr, (void*)h->ix.rel, (void*)h->ix.tl_ptr,
                     (void*)h->ix.tl_tile, (void*)h->ix.tl_start, (void*)h->ix.ldoc,
-                    (void*)h->ix.val, (void*)h->ix.bmax, (void*)h->ix.bpool})
+                    (void*)h->ix.val, (void*)h->ix.bmax, (void*)h->ix.bpool,
+                    (void*)h->ix.tmask})
       hipFree(x);
   }
   hipFree(h->ix.wbpool);  // (the handle's own pooled world bounds)
@@ -1243,6 +1261,27 @@ int bm25_index_bounds_export(bm25_index* h, uint16_t* d_out, int64_t stride, voi
   if (bs > 0)
     HIP_TRY(hipMemcpy2DAsync(d_out, sizeof(uint16_t) * stride, h->ix.bmax, sizeof(uint16_t) * bs,
                              sizeof(uint16_t) * bs, V, hipMemcpyDeviceToDevice, st),
+            "hipMemcpy2DAsync");
+  return BM25_OK;
+}
+
+int bm25_index_masks_export(bm25_index* h, uint32_t* d_out, int64_t stride, void* stream) {
+  if (!h || !d_out) return fail(BM25_EINVAL, "NULL argument");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (!h->ix.tmask)
+    return fail(BM25_EINVAL, "the index keeps no sub-block masks (tile bounds and BM25_TILE_MASK != 0 "
+                             "at create)");
+  const int64_t bs = bmax_stride(h->ix.ntiles);
+  if (stride < bs || stride % 4 != 0)
+    return fail(BM25_EINVAL, "stride %lld: a multiple of 4, >= %lld", (long long)stride, (long long)bs);
+  HIP_TRY(hipSetDevice(h->ix.device), "hipSetDevice");
+  const hipStream_t st = (hipStream_t)stream;
+  const int64_t V = h->ix.n_terms;
+  if (V == 0) return BM25_OK;
+  if (stride > bs) HIP_TRY(hipMemsetAsync(d_out, 0, sizeof(uint32_t) * V * stride, st), "hipMemsetAsync");
+  if (bs > 0)
+    HIP_TRY(hipMemcpy2DAsync(d_out, sizeof(uint32_t) * stride, h->ix.tmask, sizeof(uint32_t) * bs,
+                             sizeof(uint32_t) * bs, V, hipMemcpyDeviceToDevice, st),
             "hipMemcpy2DAsync");
   return BM25_OK;
 }

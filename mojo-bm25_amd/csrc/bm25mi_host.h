@@ -132,6 +132,12 @@ inline constexpr OptDesc kOpts[] = {
     {"bool_chunk", "BM25_BOOL_CHUNK", &SearchOpts::bool_chunk, kOptRange, 0, 1 << 30, 1,
      "bool_chunk must be in 0..2^30"},
 };
+// Options added since: a table of their own with the same rows, so the
+// first one stays the sixteen options its host check pins by count.  set_opt,
+// get_opt and a new handle's environment read both.
+inline constexpr OptDesc kOptsMore[] = {
+    {"tile_mask", "BM25_TILE_MASK", &SearchOpts::tile_mask, kOptBool, 0, 1, 0, nullptr},
+};
 
 // Sets / reads one option by name (EINVAL names the accepted values).
 int set_opt(SearchOpts& o, const char* name, int64_t v);

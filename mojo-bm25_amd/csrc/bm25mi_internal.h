@@ -91,6 +91,8 @@ struct SearchOpts {
   int filter_tiles = 1;    // filtered search, k <= kMaxK: the tile passes (0: dense score rows
                            // for every query)
   int bool_chunk = 0;      // boolean search: queries per chunk of masks (0: auto, <= 1 GiB of words)
+  int tile_mask = 1;       // the tile bound refined by the sub-block presence masks (needs tmask;
+                           // read at index build too: 0 there keeps the handle without the table)
 };
 
 // What the last search launched (bm25_search_dispatch).
@@ -107,6 +109,7 @@ enum {
   kKFiltered = 4096,   // the filtered search's tile passes (bm25mi_filter.hip)
   kKWeighted = 8192,   // (a flag) the search was weighted (bm25_search_weighted)
   kKAfter = 16384,     // (a flag) the search came through bm25_search_after(_device)
+  kKTileSkip = 32768,  // tile_skip_kernel: the tile bounds' pre-pass of a flat REST launch
 };
 struct Dispatch {
   uint32_t kernels = 0;       // kK* bits of the score kernels launched
@@ -117,6 +120,11 @@ struct Dispatch {
 
 // Row stride of the tile-bound table: whole groups of four tiles (8 B).
 __host__ __device__ inline int64_t bmax_stride(int64_t ntiles) { return (ntiles + 3) & ~(int64_t)3; }
+
+// Row bytes of the REST pass's tile-skip bitmap: a bit per tile, whole u32 words.
+__host__ __device__ inline int64_t tskip_stride(int64_t ntiles) {
+  return (((ntiles + 7) >> 3) + 3) & ~(int64_t)3;
+}
 
 struct DevIndex {
   int device = 0;
@@ -145,6 +153,12 @@ struct DevIndex {
   // bound of that score (threshold keys) and, one f16 step up, an upper bound
   // (the REST pass's tile skip)
   uint16_t* bmax = nullptr;
+  // Sub-block presence masks beside bmax, [V][bmax_stride]: bit s of (term,
+  // tile) is set when the term has a posting in the tile's s-th sub-block of
+  // 2^(tile_shift - 5) documents (zero past the last tile).  A document only
+  // collects terms whose bit of its sub-block is set, which tightens the tile
+  // bound (tile_skip_kernel); null: the whole-tile bound alone
+  uint32_t* tmask = nullptr;
   // The same bounds pooled over groups of kPool consecutive tiles (the max of
   // each group's entries, [V][pstride], pstride = bmax_stride(ceil(ntiles /
   // kPool))): the threshold kernel's input where it holds enough groups — a
@@ -270,6 +284,9 @@ struct Workspace {
   uint32_t* sub = nullptr;
   int32_t* sub_ipb = nullptr;
   int32_t* sub_done = nullptr;
+  uint8_t* tskip = nullptr;      // [Q][tskip_stride(ntiles)] bytes: bit (tile & 7) of byte tile >> 3
+                                 // set = REST skips the (query, tile) (tile_skip_kernel writes
+                                 // every word of the searched rows before each REST launch)
   uint64_t* seg = nullptr;       // sparse index: [Q][tiles/8][TT][8] segment of each (query,
                                  // term position, tile) (start | len << 32), built per search
   int64_t cap_seg = 0;           // u64 entries of seg
@@ -320,6 +337,8 @@ hipError_t launch_build_tables(const DevIndex& ix, const int32_t* d_indices,
                                int32_t* d_err, hipStream_t stream);
 // Tile bounds ix.bmax from the dense segment table and the scores.
 hipError_t launch_build_bmax(const DevIndex& ix, hipStream_t stream);
+// Sub-block presence masks ix.tmask from the dense segment table and ldoc.
+hipError_t launch_build_tmask(const DevIndex& ix, hipStream_t stream);
 // out[r][g] = the max of in[r][kPool g .. kPool g + kPool - 1] (u16 f16 bits,
 // all >= 0) for rows r < rows, g < out_stride (zero past in_stride).
 hipError_t launch_pool_bounds(const uint16_t* in, int64_t rows, int64_t in_stride, uint16_t* out,

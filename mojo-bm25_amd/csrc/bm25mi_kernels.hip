@@ -55,14 +55,15 @@ struct IndexArgs {
   const uint32_t* tl_start;
   const uint64_t* seg;      // sparse + flat kernel: this search's segment table
   int64_t seg_zero;         // ... index of a zero entry past it
-  const uint16_t* bmax;     // dense, non-negative index: f16 upper bound of each (term,
-                            // tile)'s largest score ([V][ntiles]; null: no tile bounds)
+  const uint8_t* tskip;     // flat REST with tile bounds: this search's skip bit of each
+                            // (query, tile) (tile_skip_kernel; null: no tile bounds)
+  int64_t tskip_stride;     // ... and its row bytes
 };
 
 static IndexArgs args_of(const DevIndex& ix) {
   return IndexArgs{ix.indptr, ix.rel, ix.ldoc, ix.val, ix.n_terms, ix.ntiles, ix.n_docs,
                    ix.nnz, ix.doc_offset, ix.nonneg ? 1 : 0, ix.sparse ? 1 : 0, ix.tl_ptr,
-                   ix.tl_tile, ix.tl_start, nullptr, 0, ix.opt.tile_bound ? ix.bmax : nullptr};
+                   ix.tl_tile, ix.tl_start, nullptr, 0, nullptr, 0};
 }
 
 // Segment bounds [r0, r1) (relative to indptr[term]) of a valid term in a
@@ -1050,8 +1051,8 @@ struct FlatCur {    // XCD-relative item ordinal, its claim's end, first phase t
 struct FlatDesc {   // lane tile * 2^TL + term: the term's segment in the tile (raw; r1 == r0: none)
   uint32_t ip, r0, r1;
   uint32_t aux;     // REST, one of (the launch never asks for both):
-                    //   tile bounds: f16 bits of an upper bound of the term's scores in
-                    //     the tile (one step above bmax; 0 outside the item)
+                    //   tile bounds: the tile's skip bit (tile_skip_kernel; 0 outside
+                    //     the item)
                     //   sample skip: score-key half of the tile's best sample key
 };
 
@@ -1261,7 +1262,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BM25_FLAT_WP
   };
   // REST: sample tiles (groups of G = kSampleGroup tiles, one group per G * P)
   // whose best sample key is below theta are skipped
-  const bool skipping = PH == kRest && skeys != nullptr && G == kSampleGroup && a.bmax == nullptr;
+  // (the tile bounds' skip bits: at 8 term lanes only, launch_flat)
+  constexpr bool kBits = PH == kRest && TL == 3;
+  const bool skipping = PH == kRest && skeys != nullptr && G == kSampleGroup &&
+                        !(kBits && a.tskip != nullptr);
   const uint32_t lgG = (uint32_t)__builtin_ctz((unsigned)G), lgP = (uint32_t)__builtin_ctz((unsigned)P);
   // an item's segment descriptors (4 VGPRs: a lane outside the item reads its
   // r1 from r0's address, so r1 - r0 = 0 needs no flag; the sample-tile test
@@ -1287,9 +1291,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BM25_FLAT_WP
       d.r1 = *(ok ? r + 1 : r);
     }
     d.aux = 0u;
-    if (PH == kRest && a.bmax != nullptr) {  // > the term's largest score in the tile: one
-      // f16 step above its rounded-down maximum
-      if (ok) d.aux = (uint32_t)a.bmax[tt * bmax_stride(a.ntiles) + tile] + 1u;
+    if (kBits && a.tskip != nullptr) {  // the tile's skip bit, on every lane of the
+      // item's tiles (a padding or unknown term on the tile's first lane still counts it)
+      const uint32_t t32 = (uint32_t)c.b + li;  // REST: phase tile = tile
+      if ((int)li < c.bw)
+        d.aux = ((uint32_t)a.tskip[(int64_t)c.q * a.tskip_stride + (t32 >> 3)] >> (t32 & 7u)) & 1u;
     } else if (skipping) {  // the score-key half of this tile's best sample key
       // G and P are powers of two (sample_geom): shifts, no integer division
       const uint32_t t32 = (uint32_t)tile;
@@ -1328,15 +1334,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BM25_FLAT_WP
     const bool smp = skipping && ((t32 >> lgG) & (uint32_t)(P - 1)) == 0u;
     bool skip = smp && th_pos && dN.aux < (uint32_t)(thN >> 32);
     if constexpr (PH == kRest) {
-      // tile bound: no doc of the tile can reach theta when the sum of its
-      // query terms' largest scores in the tile (every term lane of the tile,
-      // duplicates included) is below theta's score.  fp32 addition is
-      // monotone, so the query-order sum of a doc's scores is at most the sum
-      // of these maxima; the 1e-4 margin covers this tree-order sum's own
-      // rounding.  The tile runs no rows and no epilogue.
-      if (a.bmax != nullptr && th_pos) {
-        const float ub = seg_sum_f32<TL>(f16_bits_to_float((uint16_t)dN.aux));
-        const bool cut = ub * 1.0001f < key_score((uint32_t)(thN >> 32));
+      // tile bound: tile_skip_kernel found that no doc of the tile can reach
+      // theta (a bit is only ever set under a positive theta).  The tile runs
+      // no rows and no epilogue.
+      if (kBits && a.tskip != nullptr) {
+        const bool cut = dN.aux != 0u;
         // ... the tile's postings (lanes outside the item hold r1 == r0), counted
         // with the pair by the tile's first term lane (the count_skips build)
         const uint32_t tp = kCountPost ? seg_sum_u32<TL>(dN.r1 - dN.r0) : 0u;
@@ -1839,6 +1841,104 @@ __global__ __launch_bounds__(256) void build_bmax_kernel(const int64_t* __restri
       if ((float)h > m) --u;  // (inf past the range becomes 65504)
       bmax[t * bs + j] = u;
     }
+  }
+}
+
+// Sub-block presence masks beside the tile bounds: tmask[t][j] bit s = term t
+// has a posting in sub-block s (2^(S - 5) documents) of tile j — ldoc is the
+// document's byte offset in the tile's accumulator, 4 x (doc mod 2^S), so the
+// sub-block is ldoc >> (S - 3).  Rows as bmax's, zero past the last tile.
+__global__ __launch_bounds__(256) void build_tmask_kernel(const int64_t* __restrict__ indptr,
+                                                          const uint32_t* __restrict__ rel,
+                                                          const uint16_t* __restrict__ ldoc,
+                                                          int64_t V, int64_t ntiles, int S,
+                                                          uint32_t* __restrict__ tmask) {
+  const int64_t bs = bmax_stride(ntiles);
+  for (int64_t t = blockIdx.x; t < V; t += gridDim.x) {
+    const int64_t ip = indptr[t];
+    const uint32_t* r = rel + t * (ntiles + 1);
+    for (int64_t j = ntiles + threadIdx.x; j < bs; j += blockDim.x) tmask[t * bs + j] = 0u;
+    for (int64_t j = threadIdx.x; j < ntiles; j += blockDim.x) {
+      uint32_t m = 0u;
+      for (int64_t p = ip + r[j]; p < ip + r[j + 1]; ++p) m |= 1u << ((uint32_t)ldoc[p] >> (S - 3));
+      tmask[t * bs + j] = m;
+    }
+  }
+}
+
+// The REST pass's tile bounds, ahead of it (theta is known): one thread per
+// (query, tile), a block per query and kSkipNT consecutive tiles, so the
+// table rows are read coalesced along the tiles.  A tile is skipped
+// when no document of it can reach theta's score (theta > 0 only):
+//   * the whole-tile bound: the sum of its query terms' upper bounds ub (one
+//     f16 step above bmax; every term position, duplicates included; padding
+//     and unknown ids add nothing) is below theta.  fp32 addition is
+//     monotone, so the query-order sum of a doc's scores is at most the sum of
+//     these maxima; the 1e-4 margin covers the sums' own rounding;
+//   * else, with the presence masks: a document of sub-block s only collects
+//     the terms whose bit s is set, so max over s of the sum of those terms'
+//     ub bounds every document of the tile.  That sum runs in integers: ub in
+//     units of theta / 2^20, rounded up (+ 1 covers the scaling's own two
+//     roundings, values >= 2 theta saturate at 2^21: alone above theta), at
+//     most 8 of them — exact, and never below the real sum; the same 1e-4
+//     margin separates it from any fp32 sum of the scores themselves.
+// Bit (tile & 7) of byte tile >> 3 of the query's row; every u32 word of the
+// row is written (zero past the last tile, and all zero without a positive
+// theta).  tmask null: the whole-tile bound alone.
+constexpr int kSkipNT = 256;
+constexpr int kSkipTerms = 8;  // the flat kernel's 8 term lanes (launch_flat)
+__global__ __launch_bounds__(kSkipNT) void tile_skip_kernel(
+    const uint16_t* __restrict__ bmax, const uint32_t* __restrict__ tmask, int64_t V,
+    int64_t ntiles, const int32_t* __restrict__ queries, int32_t T, int64_t Q,
+    const uint64_t* __restrict__ theta, uint8_t* __restrict__ tskip) {
+  const int64_t bs = bmax_stride(ntiles), ss = tskip_stride(ntiles);
+  const int64_t nch = (ss * 8 + kSkipNT - 1) / kSkipNT;  // chunks that cover every word of a row
+  const int lane = lane_id();
+  for (int64_t it = blockIdx.x; it < Q * nch; it += gridDim.x) {
+    const int64_t q = it / nch;
+    const int64_t tile = (it - q * nch) * kSkipNT + threadIdx.x;
+    const uint32_t thk = (uint32_t)(theta[q] >> 32);
+    bool cut = false;
+    if (thk > score_key(0.f) && tile < ntiles) {
+      float ub[kSkipTerms];
+      uint32_t mk[kSkipTerms];
+#pragma unroll
+      for (int t = 0; t < kSkipTerms; ++t) {
+        ub[t] = 0.f;
+        mk[t] = 0u;
+        if (t < T) {
+          const int32_t term = queries[q * T + t];
+          if (term >= 0 && term < V) {
+            ub[t] = f16_bits_to_float((uint16_t)(bmax[term * bs + tile] + 1u));
+            if (tmask != nullptr) mk[t] = tmask[term * bs + tile];
+          }
+        }
+      }
+      // (the order of the REST kernel's former segment sum over the 8 term lanes)
+      const float sum = ((ub[0] + ub[1]) + (ub[2] + ub[3])) + ((ub[4] + ub[5]) + (ub[6] + ub[7]));
+      const float th = key_score(thk);
+      cut = sum * 1.0001f < th;
+      if (!cut && tmask != nullptr) {
+        const float K = 1048576.f / th;
+        uint32_t c[kSkipTerms];
+#pragma unroll
+        for (int t = 0; t < kSkipTerms; ++t)
+          c[t] = mk[t] != 0u ? (uint32_t)ceilf(fminf(ub[t] * K, 2097152.f)) + 1u : 0u;
+        uint32_t best = 0u;
+#pragma unroll
+        for (int s = 0; s < 32; ++s) {
+          uint32_t acc = 0u;
+#pragma unroll
+          for (int t = 0; t < kSkipTerms; ++t) acc += __umul24((mk[t] >> s) & 1u, c[t]);
+          best = max(best, acc);
+        }
+        cut = best <= 1048471u;  // best * 1.0001 < 2^20
+      }
+    }
+    const uint64_t bal = __ballot(cut);
+    const int64_t off = ((tile - lane) >> 3) + 4 * lane;  // the wave's two words: lanes 0, 1
+    if (lane < 2 && off + 4 <= ss)
+      *reinterpret_cast<uint32_t*>(tskip + q * ss + off) = (uint32_t)(bal >> (32 * lane));
   }
 }
 
@@ -3542,6 +3642,14 @@ hipError_t launch_build_bmax(const DevIndex& ix, hipStream_t stream) {
   return hipGetLastError();
 }
 
+hipError_t launch_build_tmask(const DevIndex& ix, hipStream_t stream) {
+  if (ix.n_terms == 0 || ix.ntiles == 0 || !ix.tmask || ix.sparse) return hipSuccess;
+  const int64_t blocks = std::min<int64_t>(ix.n_terms, 65536);
+  hipLaunchKernelGGL(build_tmask_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, ix.indptr,
+                     ix.rel, ix.ldoc, ix.n_terms, ix.ntiles, ix.tile_shift, ix.tmask);
+  return hipGetLastError();
+}
+
 hipError_t launch_count_tiles(const DevIndex& ix, const int32_t* d_indices, int64_t* d_cnt,
                               int32_t* d_err, hipStream_t stream) {
   if (ix.n_terms == 0) return hipSuccess;
@@ -3611,6 +3719,20 @@ SampleGeom shard_geom_world(const DevIndex& ix, int k, int64_t T, bool world) {
   return search_geom(ix, ix.ntiles, k, 1, T);
 }
 
+// Compute units of a device, cached per device (256 where the query fails).
+static int device_cus(int dev) {
+  static std::mutex mu;
+  static std::map<int, int> cache;
+  std::lock_guard<std::mutex> lk(mu);
+  const auto it = cache.find(dev);
+  if (it != cache.end()) return it->second;
+  int cus = 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
+    cus = 256;
+  cache[dev] = cus;
+  return cus;
+}
+
 // Every resident workgroup slot of the current device (a multiple of 8, one
 // per XCD round), cached per (kernel, device).
 template <class K>
@@ -3623,8 +3745,8 @@ static int persistent_grid(K kernel, int block) {
   const auto key = std::make_pair((const void*)kernel, dev);
   const auto it = cache.find(key);
   if (it != cache.end()) return it->second;
-  int cus = 0, occ = 0;
-  hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  int occ = 0;
+  const int cus = device_cus(dev);
   hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, block, 0);
   const int g = ((cus * (occ > 0 ? occ : 1) + 7) / 8) * 8;
   cache[key] = g;
@@ -3669,8 +3791,23 @@ static void launch_flat(const DevIndex& ix, const int32_t* q, int64_t T, int64_t
   IndexArgs a = args_of(ix);
   // one descriptor field: the sample keys' skip or the tile bounds; and the
   // bounds only at 8 term lanes (16 lanes: 4-tile items whose 16 bmax rows cost
-  // more than the few tiles they skip — 5.45 vs 5.00 ms, 16-term queries)
-  if (skip || TL > 3) a.bmax = nullptr;
+  // more than the few tiles they skip — 5.45 vs 5.00 ms, 16-term queries).
+  // The bounds' pre-pass writes this launch's skip bits on the same stream:
+  // after theta, before REST, no other ordering.  Not for the large-k list
+  // path: under its low theta the bound cuts too few tiles to pay for the
+  // pre-pass (k = 10 000 at config 3: 7.04 ms with it, 6.84 without any bound,
+  // 6.89 with the former in-kernel bound).
+  if (PH == kRest && !skip && !kSlots && TL == 3 && ix.opt.tile_bound && ix.bmax != nullptr &&
+      ws.tskip != nullptr) {
+    a.tskip = ws.tskip;
+    a.tskip_stride = tskip_stride(ix.ntiles);
+    const int64_t items = sg.nq_host * ((a.tskip_stride * 8 + kSkipNT - 1) / kSkipNT);
+    const int grid = (int)std::min<int64_t>(items, persistent_grid(tile_skip_kernel, kSkipNT));
+    ix.disp.kernels |= kKTileSkip;
+    hipLaunchKernelGGL(tile_skip_kernel, dim3((unsigned)grid), dim3(kSkipNT), 0, st, ix.bmax,
+                       ix.opt.tile_mask ? ix.tmask : (const uint32_t*)nullptr, ix.n_terms,
+                       ix.ntiles, q, (int32_t)T, (int64_t)sg.nq_host, ws.theta, ws.tskip);
+  }
   a.seg = ws.seg;
   a.seg_zero = Qb * ((ix.ntiles + 7) >> 3) * 8 * (1 << TL);
   const int64_t nt = PH == kSample ? sample_count(ix.ntiles, sg.P, sg.G) : ix.ntiles;
@@ -4018,9 +4155,7 @@ hipError_t launch_score(const DevIndex& ix, const int32_t* d_queries, int64_t Q,
   // split REST items where the waves get few items each (a doc shard of a
   // few GPUs' collection: ~16 at W = 8): the heavy queries' last items set
   // when the pass ends
-  static int cus = 0;
-  if (cus == 0 && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ix.device) != hipSuccess)
-    cus = 256;
+  const int cus = device_cus(ix.device);
   const bool split = ix.opt.rest_split && ws.sub != nullptr && g.P == 0 && flat_tl(T) == 3 &&
                      use_flat(ix, T, Q) && Q < (1 << 20) &&
                      ((ix.ntiles + 7) / 8) * Q < (int64_t)kSplitItemsPerWave * 19 * cus;
