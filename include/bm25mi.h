@@ -721,8 +721,11 @@ int bm25_search_stats_ex(bm25_index* idx, int64_t* rescored_tiles,
  *   [4] queries left to
  *   the block merge (lists longer than one wavefront's registers), [5] k >
  *   4096: queries the list path handed to dense score rows (-1: the dense
- *   path served the whole search; 0 after a search of k <= 4096).
- * n must be in 1..6. */
+ *   path served the whole search; 0 after a search of k <= 4096),
+ *   [6] non-empty term segments the REST pass dropped in tiles it scored
+ *   (seg_skip: the term has no posting in a sub-block that can reach the
+ *   threshold), [7] their postings — counted as [2] and [3], else -1.
+ * n must be in 1..8. */
 int bm25_search_counters(bm25_index* idx, int64_t* out, int32_t n);
 
 /*
@@ -730,8 +733,8 @@ int bm25_search_counters(bm25_index* idx, int64_t* out, int32_t n);
  * environment (BM25_FLAT, BM25_FLAT_BW, BM25_ITEMS_PER_WAVE, BM25_SAMPLE_P,
  * BM25_LIST_CAP, BM25_CLAIM_CH, BM25_CLAIM_M, BM25_TILE_BOUND, BM25_THETA_BOUND,
  * BM25_GRID_PCT, BM25_LARGE_LISTS, BM25_COUNT_SKIPS, BM25_REST_SPLIT,
- * BM25_BOUND_POOL, BM25_FILTER_TILES, BM25_BOOL_CHUNK) and, for "tile_mask",
- * from BM25_TILE_MASK, at bm25_index_create; these
+ * BM25_BOUND_POOL, BM25_FILTER_TILES, BM25_BOOL_CHUNK) and, for "tile_mask"
+ * and "seg_skip", from BM25_TILE_MASK and BM25_SEG_SKIP, at bm25_index_create; these
  * calls change or read them afterwards, effective from the next search.
  * Results never depend on them (every setting is bit-exact); they choose
  * kernels and geometry:
@@ -793,6 +796,11 @@ int bm25_search_counters(bm25_index* idx, int64_t* out, int32_t n);
  *                    whole-tile bound alone.  Read at bm25_index_create too:
  *                    a handle created under BM25_TILE_MASK=0 keeps no mask
  *                    table, and the option then changes nothing
+ *   "seg_skip"       1 (default): in a tile the REST pass scores, it drops the
+ *                    segment of every query term that has no posting in a
+ *                    sub-block whose masked bound reaches the threshold (the
+ *                    pre-pass marks them: a byte per (query, tile)); needs
+ *                    "tile_mask" and its table; 0: whole tiles only
  *   "grid_pct"      percent of the device's resident workgroup slots the
  *                    persistent score kernels launch (1..100, default 100):
  *                    below 100 leaves slots for kernels of another stream
@@ -822,7 +830,8 @@ int bm25_index_get_option(const bm25_index* idx, const char* name, int64_t* valu
  *                16384 (a flag): the last search was called through
  *                bm25_search_after(_device), whatever its cursors;
  *                32768: tile_skip_kernel, the tile bounds' pre-pass of a flat
- *                REST launch
+ *                REST launch; 65536 (a flag): the pre-pass also marked the
+ *                dead term segments of scored tiles (seg_skip)
  *   *term_lanes  flat kernel: term lanes per tile (8, 16, 32 or 64)
  *   band_tiles   [3]: flat kernel tiles per item of ALL, SAMPLE, REST
  *   *sample_p    sampling stride of the search (1: exact pass, 0: tile-bound

@@ -235,7 +235,7 @@ int ensure_ws(bm25_index* h, int64_t Q, int64_t T, int k, hipStream_t st) {
   HIP_TRY(hipMalloc(&ws.sub_ipb, sizeof(int32_t)), "hipMalloc(sub_ipb)");
   HIP_TRY(hipMalloc(&ws.sub_done, sizeof(int32_t)), "hipMalloc(sub_done)");
   HIP_TRY(hipMemsetAsync(ws.sub_done, 0, sizeof(int32_t), st), "hipMemsetAsync(sub_done)");
-  // the REST pass's tile-skip bits (tile_skip_kernel writes them per search)
+  // the REST pass's tile-skip bytes (tile_skip_kernel writes them per search)
   if (h->ix.bmax)
     HIP_TRY(hipMalloc(&ws.tskip, (size_t)std::max<int64_t>(q * tskip_stride(nt), 4)), "hipMalloc(tskip)");
   ws.cap_seg = need_seg;
@@ -1816,7 +1816,7 @@ int bm25_search_stats_ex(bm25_index* h, int64_t* rescored_tiles, int64_t* fallba
 
 int bm25_search_counters(bm25_index* h, int64_t* out, int32_t n) {
   if (!h || !out) return fail(BM25_EINVAL, "NULL argument");
-  if (n < 1 || n > 6) return fail(BM25_EINVAL, "n=%d must be in 1..6", n);
+  if (n < 1 || n > 8) return fail(BM25_EINVAL, "n=%d must be in 1..8", n);
   Enter in(h);
   if (in.rc) return in.rc;
   int32_t cnt[kCounters] = {};
@@ -1825,8 +1825,11 @@ int bm25_search_counters(bm25_index* h, int64_t* out, int32_t n) {
   std::memcpy(&post, cnt + 6, sizeof post);  // counters[6..7]: a u64 (score_flat_kernel)
   // (the skipped pairs and postings: counted by the count_skips build only, else -1)
   const bool counted = (h->ix.disp.kernels & kKCountSkips) != 0;
-  const int64_t v[6] = {cnt[3], cnt[2], counted ? cnt[5] : -1, counted ? (int64_t)post : -1,
-                        cnt[4], h->large_fallback};
+  uint64_t dpost = 0;
+  std::memcpy(&dpost, cnt + 10, sizeof dpost);  // counters[10..11]: the dropped segments' postings
+  const int64_t v[8] = {cnt[3], cnt[2], counted ? cnt[5] : -1, counted ? (int64_t)post : -1,
+                        cnt[4], h->large_fallback, counted ? cnt[8] : -1,
+                        counted ? (int64_t)dpost : -1};
   for (int i = 0; i < n; ++i) out[i] = v[i];
   return BM25_OK;
 }

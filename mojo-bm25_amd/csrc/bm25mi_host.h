@@ -137,6 +137,7 @@ inline constexpr OptDesc kOpts[] = {
 // get_opt and a new handle's environment read both.
 inline constexpr OptDesc kOptsMore[] = {
     {"tile_mask", "BM25_TILE_MASK", &SearchOpts::tile_mask, kOptBool, 0, 1, 0, nullptr},
+    {"seg_skip", "BM25_SEG_SKIP", &SearchOpts::seg_skip, kOptBool, 0, 1, 0, nullptr},
 };
 
 // Sets / reads one option by name (EINVAL names the accepted values).

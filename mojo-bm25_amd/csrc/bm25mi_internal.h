@@ -93,6 +93,8 @@ struct SearchOpts {
   int bool_chunk = 0;      // boolean search: queries per chunk of masks (0: auto, <= 1 GiB of words)
   int tile_mask = 1;       // the tile bound refined by the sub-block presence masks (needs tmask;
                            // read at index build too: 0 there keeps the handle without the table)
+  int seg_skip = 1;        // REST drops the term segments of a scored tile that lie in dead
+                           // sub-blocks only (the pre-pass's per-lane bits; needs tile_mask)
 };
 
 // What the last search launched (bm25_search_dispatch).
@@ -110,6 +112,7 @@ enum {
   kKWeighted = 8192,   // (a flag) the search was weighted (bm25_search_weighted)
   kKAfter = 16384,     // (a flag) the search came through bm25_search_after(_device)
   kKTileSkip = 32768,  // tile_skip_kernel: the tile bounds' pre-pass of a flat REST launch
+  kKSegSkip = 65536,   // (a flag) ... and it marked the dead term segments of scored tiles
 };
 struct Dispatch {
   uint32_t kernels = 0;       // kK* bits of the score kernels launched
@@ -121,10 +124,8 @@ struct Dispatch {
 // Row stride of the tile-bound table: whole groups of four tiles (8 B).
 __host__ __device__ inline int64_t bmax_stride(int64_t ntiles) { return (ntiles + 3) & ~(int64_t)3; }
 
-// Row bytes of the REST pass's tile-skip bitmap: a bit per tile, whole u32 words.
-__host__ __device__ inline int64_t tskip_stride(int64_t ntiles) {
-  return (((ntiles + 7) >> 3) + 3) & ~(int64_t)3;
-}
+// Row bytes of the REST pass's tile-skip table: a byte per tile, whole u32 words.
+__host__ __device__ inline int64_t tskip_stride(int64_t ntiles) { return (ntiles + 3) & ~(int64_t)3; }
 
 struct DevIndex {
   int device = 0;
@@ -190,7 +191,7 @@ struct DevIndex {
   mutable Dispatch disp;  // written by the launchers (callers hold the handle's mutex)
 };
 
-constexpr int kCounters = 8;  // Workspace::counters
+constexpr int kCounters = 12;  // Workspace::counters
 
 // A handle's reusable scratch for the large-k paths (bm25mi_large.hip): one
 // device allocation, bump-allocated by each search (nested uses stack), sized
@@ -263,7 +264,9 @@ struct Workspace {
                                  // [2] fallback queries, [3] tiles re-scored this search,
                                  // [4] queries left to the block merge (slow),
                                  // [5] (query, tile) pairs REST skipped by their tile bound,
-                                 // [6..7] (a u64) the postings of those pairs
+                                 // [6..7] (a u64) the postings of those pairs,
+                                 // [8] term segments REST dropped in the tiles it scored,
+                                 // [10..11] (a u64) their postings ([9]: unused)
   int32_t* slow = nullptr;       // [Q] those queries
   // the large-k list path's REST (bm25mi_large.hip sets them on its copy):
   // per-(query, tile) slots of slot_cap keys and their counts; null otherwise
@@ -284,9 +287,10 @@ struct Workspace {
   uint32_t* sub = nullptr;
   int32_t* sub_ipb = nullptr;
   int32_t* sub_done = nullptr;
-  uint8_t* tskip = nullptr;      // [Q][tskip_stride(ntiles)] bytes: bit (tile & 7) of byte tile >> 3
-                                 // set = REST skips the (query, tile) (tile_skip_kernel writes
-                                 // every word of the searched rows before each REST launch)
+  uint8_t* tskip = nullptr;      // [Q][tskip_stride(ntiles)]: a byte per (query, tile) — bit t
+                                 // set = REST drops term lane t's segment, 0xFF = it skips the
+                                 // tile (tile_skip_kernel writes every word of the searched
+                                 // rows before each REST launch)
   uint64_t* seg = nullptr;       // sparse index: [Q][tiles/8][TT][8] segment of each (query,
                                  // term position, tile) (start | len << 32), built per search
   int64_t cap_seg = 0;           // u64 entries of seg

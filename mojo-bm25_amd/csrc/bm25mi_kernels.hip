@@ -1263,7 +1263,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BM25_FLAT_WP
   // REST: sample tiles (groups of G = kSampleGroup tiles, one group per G * P)
   // whose best sample key is below theta are skipped
   // (the tile bounds' skip bits: at 8 term lanes only, launch_flat)
-  constexpr bool kBits = PH == kRest && TL == 3;
+  constexpr bool kBits = PH == kRest && TL == 3 && SM != kLargeM;
   const bool skipping = PH == kRest && skeys != nullptr && G == kSampleGroup &&
                         !(kBits && a.tskip != nullptr);
   const uint32_t lgG = (uint32_t)__builtin_ctz((unsigned)G), lgP = (uint32_t)__builtin_ctz((unsigned)P);
@@ -1291,11 +1291,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BM25_FLAT_WP
       d.r1 = *(ok ? r + 1 : r);
     }
     d.aux = 0u;
-    if (kBits && a.tskip != nullptr) {  // the tile's skip bit, on every lane of the
-      // item's tiles (a padding or unknown term on the tile's first lane still counts it)
+    if (kBits && a.tskip != nullptr) {  // this term lane's bit of the tile's byte, on every
+      // lane of the item's tiles: its segment is dropped (all eight: the tile is cut, and a
+      // padding or unknown term on the tile's first lane still counts it)
       const uint32_t t32 = (uint32_t)c.b + li;  // REST: phase tile = tile
       if ((int)li < c.bw)
-        d.aux = ((uint32_t)a.tskip[(int64_t)c.q * a.tskip_stride + (t32 >> 3)] >> (t32 & 7u)) & 1u;
+        d.aux = ((uint32_t)a.tskip[(int64_t)c.q * a.tskip_stride + t32] >> lt) & 1u;
     } else if (skipping) {  // the score-key half of this tile's best sample key
       // G and P are powers of two (sample_geom): shifts, no integer division
       const uint32_t t32 = (uint32_t)tile;
@@ -1309,12 +1310,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BM25_FLAT_WP
     return (uint32_t)(th >> 32) > score_key(0.f);
   };
 
-  uint32_t nbound = 0;  // REST: (query, tile) pairs this lane's tiles skipped by their bound
-  // ... and the postings of this lane's skipped segments.  Both only in the
-  // REST build of the count_skips option (SM == 2): the two live registers
-  // cost the pass 13 % on an 8-way doc shard (profiles/r05/counters)
+  uint32_t nbound = 0;  // REST: (query, tile) pairs this wave's tiles skipped by their bound
+  // ... and the postings of their segments.  Both only in the REST build of
+  // the count_skips option (SM == 2), whose counting costs the pass 13 % on
+  // an 8-way doc shard (profiles/r05/counters); wave sums, so scalar registers
   constexpr bool kCountPost = PH == kRest && SM == 2;
   uint32_t npost = 0;
+  // ... and the non-empty segments this wave dropped in tiles that were scored, with their postings
+  uint32_t ndrop = 0, ndpost = 0;
   // ---- the issue side's item: its segments (lane s = tile * TT + term) and
   // row numbering; the item prefetch pipeline one and two items ahead
   uint32_t iSb = 0, iSl = 0, iIncl = 0, iExcl = 0;
@@ -1337,16 +1340,26 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BM25_FLAT_WP
       // tile bound: tile_skip_kernel found that no doc of the tile can reach
       // theta (a bit is only ever set under a positive theta).  The tile runs
       // no rows and no epilogue.
+      // A scored tile's lane whose bit is set drops its segment alone: the
+      // term has no posting in a sub-block that can reach theta.  Its tile
+      // starts on the first remaining row, as with an absent term.
       if (kBits && a.tskip != nullptr) {
-        const bool cut = dN.aux != 0u;
-        // ... the tile's postings (lanes outside the item hold r1 == r0), counted
-        // with the pair by the tile's first term lane (the count_skips build)
-        const uint32_t tp = kCountPost ? seg_sum_u32<TL>(dN.r1 - dN.r0) : 0u;
-        if (kCountPost && cut && !skip && lt == 0u && (int)li < nx.bw) {
-          ++nbound;
-          npost += tp;
+        const bool drop = dN.aux != 0u;
+        if constexpr (kCountPost) {
+          // the count_skips build: a cut tile sets all eight lanes; its postings
+          // (lanes outside the item hold r1 == r0) are counted with the pair by
+          // the tile's first term lane, a dropped segment's by its own lane
+          const bool cut = seg_sum_u32<TL>(dN.aux) == TT;
+          const uint32_t sl = dN.r1 - dN.r0;
+          const uint32_t tp = seg_sum_u32<TL>(sl);
+          const bool cnt = cut && !skip && lt == 0u && (int)li < nx.bw;
+          nbound += (uint32_t)__popcll(__ballot(cnt));
+          npost += wave_sum_u32(cnt ? tp : 0u);
+          const bool dcnt = drop && !cut && !skip && sl != 0u;
+          ndrop += (uint32_t)__popcll(__ballot(dcnt));
+          ndpost += wave_sum_u32(dcnt ? sl : 0u);
         }
-        skip = skip || cut;
+        skip = skip || drop;
       }
     }
     iSb = dN.ip + dN.r0;
@@ -1626,12 +1639,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BM25_FLAT_WP
 #endif
   if (curTi != kNoTile) epilogue();
   if (kCountPost && stats != nullptr) {  // bound-skipped tiles and postings of this wave
-    const uint32_t nb = wave_sum_u32(nbound);
+    const uint32_t nb = nbound;
     if (lane == 0 && nb != 0u) atomicAdd(stats, (int32_t)nb);
     // stats + 1 .. + 2: a u64 count (Workspace::counters[6..7], 8-B aligned)
-    const uint32_t np = wave_sum_u32(npost);
+    const uint32_t np = npost;
     if (lane == 0 && np != 0u)
       atomicAdd(reinterpret_cast<unsigned long long*>(stats + 1), (unsigned long long)np);
+    // stats + 3, + 5 .. + 6: the dropped segments and (a u64) their postings
+    // (Workspace::counters[8], [10..11])
+    const uint32_t nd = ndrop;
+    if (lane == 0 && nd != 0u) atomicAdd(stats + 3, (int32_t)nd);
+    const uint32_t ndp = ndpost;
+    if (lane == 0 && ndp != 0u)
+      atomicAdd(reinterpret_cast<unsigned long long*>(stats + 5), (unsigned long long)ndp);
   }
   // every claim of this wave has returned (the last one, read by next(), ran
   // out of items) before it counts itself finished
@@ -1866,9 +1886,9 @@ __global__ __launch_bounds__(256) void build_tmask_kernel(const int64_t* __restr
   }
 }
 
-// The REST pass's tile bounds, ahead of it (theta is known): one thread per
-// (query, tile), a block per query and kSkipNT consecutive tiles, so the
-// table rows are read coalesced along the tiles.  A tile is skipped
+// The REST pass's tile bounds, ahead of it (theta is known): a block per
+// query and kSkipNT * N consecutive tiles (N below), so the table rows are read
+// coalesced along the tiles.  A tile is skipped
 // when no document of it can reach theta's score (theta > 0 only):
 //   * the whole-tile bound: the sum of its query terms' upper bounds ub (one
 //     f16 step above bmax; every term position, duplicates included; padding
@@ -1882,63 +1902,106 @@ __global__ __launch_bounds__(256) void build_tmask_kernel(const int64_t* __restr
 //     roundings, values >= 2 theta saturate at 2^21: alone above theta), at
 //     most 8 of them — exact, and never below the real sum; the same 1e-4
 //     margin separates it from any fp32 sum of the scores themselves.
-// Bit (tile & 7) of byte tile >> 3 of the query's row; every u32 word of the
-// row is written (zero past the last tile, and all zero without a positive
-// theta).  tmask null: the whole-tile bound alone.
+// A tile that is not cut also gets its live mask L: bit s set iff the integer
+// sum of sub-block s exceeds the margin (the compare that decides the cut: the
+// tile is cut iff L == 0).  With `seg`, term lane t of such a tile is dropped
+// iff (mk[t] & L) == 0 — the term has no posting in any live sub-block, so it
+// only adds to documents whose full sum stays below theta.
+// One byte per (query, tile): bit t = lane t's segment is dropped, 0xFF = the
+// tile is cut, 0 = everything is scored (always without a positive theta, and
+// past the last tile).  Every u32 word of the row is written.  tmask null:
+// the whole-tile bound alone (bytes 0 or 0xFF).
+// A thread takes N = 1, 2 or 4 consecutive tiles: one wide load per table row
+// brings all of them (rows are whole groups of four tiles, bmax_stride), the
+// 2 x 8 loads of a thread are in flight together, and its bytes leave as one
+// store.  The tiles then run one after the other through the same registers,
+// so N is the most that still fills a block's threads (skip_npt): a short
+// row spreads over more threads instead.
 constexpr int kSkipNT = 256;
 constexpr int kSkipTerms = 8;  // the flat kernel's 8 term lanes (launch_flat)
+inline int skip_npt(int64_t ntiles) {
+  const int64_t bs = bmax_stride(ntiles);
+  return bs >= 4 * kSkipNT ? 4 : (bs >= 2 * kSkipNT ? 2 : 1);
+}
+// sum + kSkipBias has bit 31 set iff sum > 1048471 (sum * 1.0001 >= 2^20); sums stay below 2^25
+constexpr uint32_t kSkipBias = 0x80000000u - 1048472u;
+template <int N> struct alignas(2 * N) SkipB { uint16_t v[N]; };
+template <int N> struct alignas(4 * N) SkipM { uint32_t v[N]; };
+template <int N> struct alignas(N) SkipO { uint8_t v[N]; };
+template <int N>
 __global__ __launch_bounds__(kSkipNT) void tile_skip_kernel(
     const uint16_t* __restrict__ bmax, const uint32_t* __restrict__ tmask, int64_t V,
     int64_t ntiles, const int32_t* __restrict__ queries, int32_t T, int64_t Q,
-    const uint64_t* __restrict__ theta, uint8_t* __restrict__ tskip) {
-  const int64_t bs = bmax_stride(ntiles), ss = tskip_stride(ntiles);
-  const int64_t nch = (ss * 8 + kSkipNT - 1) / kSkipNT;  // chunks that cover every word of a row
-  const int lane = lane_id();
+    const uint64_t* __restrict__ theta, uint8_t* __restrict__ tskip, int32_t seg) {
+  const int64_t bs = bmax_stride(ntiles);  // == tskip_stride(ntiles)
+  const int64_t nch = (bs + kSkipNT * N - 1) / (kSkipNT * N);  // chunks that cover a row
   for (int64_t it = blockIdx.x; it < Q * nch; it += gridDim.x) {
     const int64_t q = it / nch;
-    const int64_t tile = (it - q * nch) * kSkipNT + threadIdx.x;
+    const int64_t t0 = ((it - q * nch) * kSkipNT + threadIdx.x) * N;  // the thread's first tile
+    if (t0 >= bs) continue;  // (bs is a multiple of 4: the whole group lies in the row)
     const uint32_t thk = (uint32_t)(theta[q] >> 32);
-    bool cut = false;
-    if (thk > score_key(0.f) && tile < ntiles) {
-      float ub[kSkipTerms];
-      uint32_t mk[kSkipTerms];
+    SkipO<N> out;
+#pragma unroll
+    for (int i = 0; i < N; ++i) out.v[i] = 0;
+    if (thk > score_key(0.f) && t0 < ntiles) {
+      SkipB<N> bb[kSkipTerms];
+      SkipM<N> mm[kSkipTerms];
+      uint32_t okm = 0u;  // (uniform) the term lanes with a known term
 #pragma unroll
       for (int t = 0; t < kSkipTerms; ++t) {
-        ub[t] = 0.f;
-        mk[t] = 0u;
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+          bb[t].v[i] = 0;
+          mm[t].v[i] = 0u;
+        }
         if (t < T) {
           const int32_t term = queries[q * T + t];
           if (term >= 0 && term < V) {
-            ub[t] = f16_bits_to_float((uint16_t)(bmax[term * bs + tile] + 1u));
-            if (tmask != nullptr) mk[t] = tmask[term * bs + tile];
+            okm |= 1u << t;
+            bb[t] = *reinterpret_cast<const SkipB<N>*>(bmax + term * bs + t0);
+            if (tmask != nullptr) mm[t] = *reinterpret_cast<const SkipM<N>*>(tmask + term * bs + t0);
           }
         }
       }
-      // (the order of the REST kernel's former segment sum over the 8 term lanes)
-      const float sum = ((ub[0] + ub[1]) + (ub[2] + ub[3])) + ((ub[4] + ub[5]) + (ub[6] + ub[7]));
       const float th = key_score(thk);
-      cut = sum * 1.0001f < th;
-      if (!cut && tmask != nullptr) {
-        const float K = 1048576.f / th;
-        uint32_t c[kSkipTerms];
+      const float K = 1048576.f / th;
 #pragma unroll
-        for (int t = 0; t < kSkipTerms; ++t)
-          c[t] = mk[t] != 0u ? (uint32_t)ceilf(fminf(ub[t] * K, 2097152.f)) + 1u : 0u;
-        uint32_t best = 0u;
+      for (int i = 0; i < N; ++i) {
+        if (t0 + i >= ntiles) break;  // (bytes past the last tile stay 0)
+        float ub[kSkipTerms];
+        uint32_t mk[kSkipTerms];
 #pragma unroll
-        for (int s = 0; s < 32; ++s) {
-          uint32_t acc = 0u;
-#pragma unroll
-          for (int t = 0; t < kSkipTerms; ++t) acc += __umul24((mk[t] >> s) & 1u, c[t]);
-          best = max(best, acc);
+        for (int t = 0; t < kSkipTerms; ++t) {
+          ub[t] = ((okm >> t) & 1u) ? f16_bits_to_float((uint16_t)(bb[t].v[i] + 1u)) : 0.f;
+          mk[t] = mm[t].v[i];
         }
-        cut = best <= 1048471u;  // best * 1.0001 < 2^20
+        // (the order of the REST kernel's former segment sum over the 8 term lanes)
+        const float sum = ((ub[0] + ub[1]) + (ub[2] + ub[3])) + ((ub[4] + ub[5]) + (ub[6] + ub[7]));
+        uint32_t byte = sum * 1.0001f < th ? 0xFFu : 0u;
+        if (byte == 0u && tmask != nullptr) {
+          uint32_t c[kSkipTerms];
+#pragma unroll
+          for (int t = 0; t < kSkipTerms; ++t)
+            c[t] = mk[t] != 0u ? (uint32_t)ceilf(fminf(ub[t] * K, 2097152.f)) + 1u : 0u;
+          uint32_t L = 0u;
+#pragma unroll
+          for (int s = 31; s >= 0; --s) {
+            uint32_t acc = kSkipBias;
+#pragma unroll
+            for (int t = 0; t < kSkipTerms; ++t) acc += __umul24((mk[t] >> s) & 1u, c[t]);
+            L = __builtin_amdgcn_alignbit(L, acc, 31);  // L << 1 | (sum_s > margin)
+          }
+          if (L == 0u) {
+            byte = 0xFFu;
+          } else if (seg) {
+#pragma unroll
+            for (int t = 0; t < kSkipTerms; ++t) byte |= (mk[t] & L) == 0u ? 1u << t : 0u;
+          }
+        }
+        out.v[i] = (uint8_t)byte;
       }
     }
-    const uint64_t bal = __ballot(cut);
-    const int64_t off = ((tile - lane) >> 3) + 4 * lane;  // the wave's two words: lanes 0, 1
-    if (lane < 2 && off + 4 <= ss)
-      *reinterpret_cast<uint32_t*>(tskip + q * ss + off) = (uint32_t)(bal >> (32 * lane));
+    *reinterpret_cast<SkipO<N>*>(tskip + q * bs + t0) = out;
   }
 }
 
@@ -3801,12 +3864,23 @@ static void launch_flat(const DevIndex& ix, const int32_t* q, int64_t T, int64_t
       ws.tskip != nullptr) {
     a.tskip = ws.tskip;
     a.tskip_stride = tskip_stride(ix.ntiles);
-    const int64_t items = sg.nq_host * ((a.tskip_stride * 8 + kSkipNT - 1) / kSkipNT);
-    const int grid = (int)std::min<int64_t>(items, persistent_grid(tile_skip_kernel, kSkipNT));
-    ix.disp.kernels |= kKTileSkip;
-    hipLaunchKernelGGL(tile_skip_kernel, dim3((unsigned)grid), dim3(kSkipNT), 0, st, ix.bmax,
-                       ix.opt.tile_mask ? ix.tmask : (const uint32_t*)nullptr, ix.n_terms,
-                       ix.ntiles, q, (int32_t)T, (int64_t)sg.nq_host, ws.theta, ws.tskip);
+    const uint32_t* tmask = ix.opt.tile_mask ? ix.tmask : (const uint32_t*)nullptr;
+    // the dead term segments of scored tiles: from the live mask, so with the masks only
+    const bool seg = ix.opt.seg_skip && tmask != nullptr;
+    ix.disp.kernels |= kKTileSkip | (seg ? kKSegSkip : 0);
+    auto pre = [&](auto kern, int npt) {
+      const int64_t per = (int64_t)kSkipNT * npt;
+      const int64_t items = sg.nq_host * ((a.tskip_stride + per - 1) / per);
+      const int grid = (int)std::min<int64_t>(items, persistent_grid(kern, kSkipNT));
+      hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kSkipNT), 0, st, ix.bmax, tmask,
+                         ix.n_terms, ix.ntiles, q, (int32_t)T, (int64_t)sg.nq_host, ws.theta,
+                         ws.tskip, (int32_t)seg);
+    };
+    switch (skip_npt(ix.ntiles)) {
+      case 4: pre(tile_skip_kernel<4>, 4); break;
+      case 2: pre(tile_skip_kernel<2>, 2); break;
+      default: pre(tile_skip_kernel<1>, 1); break;
+    }
   }
   a.seg = ws.seg;
   a.seg_zero = Qb * ((ix.ntiles + 7) >> 3) * 8 * (1 << TL);
