@@ -522,6 +522,80 @@ int bm25_search_boolean(bm25_index* idx, const int32_t* queries, int64_t Q, int6
                         int32_t* out_docs, float* out_scores);
 
 /*
+ * Minimum-should-match and hit counts: "at least m of these terms" in the any
+ * clause of the boolean term filters, and the number of documents a mask
+ * allows, both on the device.  Replaces no reference call.
+ *   The definitions of "Boolean term filters" above hold as they are.  One
+ *   more input per row, min_match [M] int32, changes only the any line of
+ *   allowed(m, d):
+ *     n_any(m)    = number of slots j of any[m] with any[m][j] >= 0
+ *     count(m, d) = number of slots j with any[m][j] >= 0 and has(any[m][j], d)
+ *     any-clause(m, d) =  n_any(m) == 0        (no id: the clause is absent,
+ *                                               min_match[m] is not read into the result)
+ *                      or min_match[m] <= 0    (the clause is optional: no constraint)
+ *                      or count(m, d) >= min_match[m]
+ *   Every non-negative slot is a clause of its own: a repeated id counts each
+ *   time it occurs (as a repeated query id is scored each time it occurs), so
+ *   any = [t, t] with min_match 2 is has(t, .); duplicates stay harmless at
+ *   min_match 1.  min_match[m] > n_any(m) allows no document: the row is all
+ *   zeros and no posting is read for it.  min_match[m] == 1, or a NULL
+ *   min_match pointer: the row is bit for bit bm25_term_masks' row.  must,
+ *   must_not, base (Mb in {0, 1, M}), the cleared tail bits, "every word of
+ *   every row is written" and "nothing at index >= W is touched" are unchanged.
+ *   bm25_term_masks_min_match: bm25_term_masks with min_match; host buffers,
+ *     validated, synchronous.  Errors: those of bm25_term_masks;
+ *     min_match[m] < 0 (the message names row and value); B > 65535 together
+ *     with a non-NULL min_match (the width of the per-document counter).
+ *     M == 0 returns BM25_OK without device work.
+ *   bm25_term_masks_min_match_device: bm25_term_masks_device with
+ *     d_min_match [M] on the device; checks shapes (B > 65535 with a non-NULL
+ *     d_min_match among them) and NULL pointers only, never synchronises,
+ *     retains no scratch, reads the immutable index arrays only and is not
+ *     ordered against the handle's searches.  An entry <= 0 means "optional".
+ *     An id >= n_terms in any is, as there, a term that no document has: it
+ *     counts in n_any and never in count.
+ *   bm25_mask_count / bm25_mask_count_device: masks [M, W] uint32 ->
+ *     out_counts [M] int64, out_counts[m] = the number of set bits of row m
+ *     among bits 0 .. n_docs - 1.  Bits at or past n_docs in the last word
+ *     are ignored even when set (a caller's own mask may carry garbage there;
+ *     the search ignores those bits too).  The caller need not zero the
+ *     counts; M may pass 65535; the result is an integer sum and does not
+ *     depend on scheduling.  On doc shards the bits are the handle's own
+ *     documents, so the shards' counts add up to the collection's.  The
+ *     device call reads the caller's masks only, never synchronises, retains
+ *     no scratch and is not ordered against the handle's searches.
+ *   Neither the mask calls nor the counts are searches: they leave
+ *   bm25_search_dispatch, the counters and bm25_search_filtered_stats alone.
+ *   bm25_search_boolean_min_match: bm25_search_boolean with the new clause:
+ *     row q is bit for bit bm25_search_filtered's row under the mask of clause
+ *     row q, and out_total_hits [Q] int64 (or NULL) receives that mask's
+ *     count.  Same chunking (option "bool_chunk", at most 1 GiB of mask
+ *     words); each chunk's counts are taken on the device before its mask
+ *     buffer is reused, so the masks still never move to the host.  k == 0
+ *     with a non-NULL out_total_hits still builds and counts the masks ("how
+ *     many match" is a query of its own; queries, out_docs and out_scores may
+ *     then be NULL).  With min_match NULL and out_total_hits NULL the outputs
+ *     equal bm25_search_boolean's.
+ */
+int bm25_term_masks_min_match(bm25_index* idx, const int32_t* must, int64_t A, const int32_t* any,
+                              int64_t B, const int32_t* must_not, int64_t N,
+                              const int32_t* min_match, int64_t M, const uint32_t* base,
+                              int64_t Mb, uint32_t* out_masks);
+int bm25_term_masks_min_match_device(bm25_index* idx, const int32_t* d_must, int64_t A,
+                                     const int32_t* d_any, int64_t B, const int32_t* d_must_not,
+                                     int64_t N, const int32_t* d_min_match, int64_t M,
+                                     const uint32_t* d_base, int64_t Mb, uint32_t* d_out_masks,
+                                     void* stream);
+int bm25_mask_count(bm25_index* idx, const uint32_t* masks, int64_t M, int64_t* out_counts);
+int bm25_mask_count_device(bm25_index* idx, const uint32_t* d_masks, int64_t M, int64_t* d_counts,
+                           void* stream);
+int bm25_search_boolean_min_match(bm25_index* idx, const int32_t* queries, int64_t Q, int64_t T,
+                                  int32_t k, const int32_t* must, int64_t A, const int32_t* any,
+                                  int64_t B, const int32_t* must_not, int64_t N,
+                                  const int32_t* min_match, const uint32_t* base, int64_t Mb,
+                                  int32_t* out_docs, float* out_scores, int64_t* out_total_hits);
+
+/*
  * bm25.BM25's float64 path (the dense model's API keeps the reference's
  * precision).  bm25_index_set_values_f64 keeps a float64 copy of the index's
  * values beside it (the same CSC order; bm25_build_scores method 1 returns

@@ -237,7 +237,7 @@ class BM25v:
         return self._gpu.search_after(queries, top_k, after, weights, allow, qm)
 
     def search_boolean(self, queries, top_k: int, must=None, any=None, must_not=None,
-                       base=None) -> Tuple[np.ndarray, np.ndarray]:
+                       base=None, *, min_match=None, total_hits: bool = False):
         """search under boolean term filters (not in the reference, whose
         search has no term filter): query q ranks only the documents that hold
         every term of ``must[q]``, at least one of ``any[q]`` (when it names
@@ -245,13 +245,19 @@ class BM25v:
         allows (a bool [n_docs] mask for every query or [Q, n_docs], or packed
         rows of bm25mi.pack_mask).  Clauses are int32 [Q, width] arrays or
         ragged lists of lists of token ids (negative = padding), or None.
-        Returns search_filtered's tuple; the masks are built on the GPU."""
+        ``min_match``: query q needs min_match[q] of the terms ``any[q]``
+        names instead of one (an int, an int [Q] array or "NN%", as
+        bm25mi.min_match_rows; 0: the clause is optional).  Returns
+        search_filtered's tuple, with ``total_hits=True`` followed by the
+        int64 [Q] number of documents each query's filter lets through; the
+        masks are built and counted on the GPU."""
         if len(queries) == 0:
-            return np.zeros((0, 0), dtype=self.dtype), np.zeros((0, 0), dtype=self.dtype)
+            empty = np.zeros((0, 0), dtype=self.dtype), np.zeros((0, 0), dtype=self.dtype)
+            return empty + (np.zeros(0, np.int64),) if total_hits else empty
         if (not isinstance(queries, np.ndarray) or queries.ndim != 2
                 or not isinstance(queries[0][0], TokId)):
             raise ValueError("The queries must be a list of list of query token IDs.")
-        from bm25mi.index import pad_clause
+        from bm25mi.index import min_match_rows, pad_clause
         Q = queries.shape[0]
         clauses = []
         for name, c in (("must", must), ("any", any), ("must_not", must_not)):
@@ -264,6 +270,9 @@ class BM25v:
             if base.ndim not in (1, 2) or (base.ndim == 2 and base.shape[0] not in (1, Q)):
                 raise ValueError("base must be a [n_docs] mask or a [Q, n_docs] array with one "
                                  "row per query.")
+        if min_match is not None:
+            min_match = min_match_rows(np.zeros((Q, 0), np.int32) if clauses[1] is None
+                                       else clauses[1], min_match, "query")
         if top_k < 0:
             raise ValueError("negative dimensions are not allowed")
         max_token_id = max([int(queries.max(initial=0))]
@@ -275,7 +284,8 @@ class BM25v:
                 "of tokens in the index.")
         if self._gpu is None:
             raise ValueError("BM25v index not built. Call index() first.")
-        return self._gpu.search_boolean(queries, top_k, clauses[0], clauses[1], clauses[2], base)
+        return self._gpu.search_boolean(queries, top_k, clauses[0], clauses[1], clauses[2], base,
+                                        min_match=min_match, total_hits=total_hits)
 
     def _compute_relevance_from_scores(self, queries, top_k: int, dtype=np.float32):
         """bm25_native.py:129-158 on the GPU: per query, negative ids dropped,

@@ -60,6 +60,38 @@ def pad_clause(rows) -> np.ndarray:
     return np.ascontiguousarray(rows, dtype=np.int32)
 
 
+def min_match_rows(any_rows, spec, what: str = "mask") -> np.ndarray:
+    """The min_match argument of the boolean term filters -> int32 [M], one
+    entry per row of ``any_rows`` (clause rows as pad_clause takes them).
+    ``spec``: an int (every row), an int array [M], or a percentage string
+    "NN%" of each row's terms — (n_any(row) * NN) // 100 in integer arithmetic
+    (rounded down, as Lucene does), raised to 1 where the row names a term; a
+    row without a term gets 0.  Wrong lengths, negative values and
+    non-integers raise ValueError."""
+    a = pad_clause(any_rows)
+    M = a.shape[0]
+    if isinstance(spec, str):
+        s = spec.strip()
+        if not (s.endswith("%") and s[:-1].isdigit() and int(s[:-1]) <= 100):
+            raise ValueError(f"min_match {spec!r}: a percentage is written \"NN%\", NN in 0..100")
+        n_any = (a >= 0).sum(axis=1).astype(np.int64)
+        mm = n_any * int(s[:-1]) // 100
+        return np.where(n_any > 0, np.maximum(mm, 1), 0).astype(np.int32)
+    mm = np.asarray(spec)
+    if mm.dtype.kind not in "iu" or mm.ndim > 1:
+        raise ValueError("min_match must be an int, an int [M] array or a string \"NN%\"")
+    if mm.ndim == 0:
+        mm = np.full(M, mm)
+    if mm.shape[0] != M:
+        raise ValueError(f"min_match has {mm.shape[0]} entries, expected {M} (one per {what})")
+    if mm.size and int(mm.min()) < 0:
+        r = int(np.argmax(mm < 0))
+        raise ValueError(f"min_match[{r}] = {int(mm[r])} is negative")
+    if mm.size and int(mm.max()) > np.iinfo(np.int32).max:
+        raise ValueError("min_match entries must fit int32")
+    return np.ascontiguousarray(mm, dtype=np.int32)
+
+
 AFTER_NONE = -2  # BM25_AFTER_NONE: an after-docs entry that means "no cursor"
 
 
@@ -690,32 +722,51 @@ class GpuIndex:
         out = [np.zeros((M, 0), np.int32) if a is None else a for a in out]
         return out[0], out[1], out[2], M, b, Mb
 
-    def term_masks(self, must=None, any=None, must_not=None, base=None) -> np.ndarray:
+    def term_masks(self, must=None, any=None, must_not=None, base=None, *,
+                   min_match=None) -> np.ndarray:
         """Allow-masks of boolean term filters (bm25_term_masks, host arrays)
         -> packed uint32 [M, W], W = ceil(n_docs / 32), the masks
         search_filtered takes: row m allows the documents of this handle that
         hold every term of must[m], at least one of any[m] (when it names
         one), none of must_not[m], and that base allows.  Clauses: int32
         [M, width] arrays or ragged lists of lists (negative ids = padding);
-        base: bool [n_docs] / [M, n_docs] or packed uint32 rows, 1 or M."""
+        base: bool [n_docs] / [M, n_docs] or packed uint32 rows, 1 or M.
+        min_match (bm25_term_masks_min_match): row m needs min_match[m] of the
+        slots of any[m] that hold an id (a repeated id counts each time; 0:
+        the clause is optional) — what min_match_rows takes: an int, an int
+        [M] array or "NN%"."""
         mu, an, mn, M, b, Mb = self._clauses_arg(must, any, must_not, base)
+        mm = None if min_match is None else min_match_rows(an, min_match)
         out = np.zeros((M, (self.n_docs + 31) // 32), np.uint32)
-        check(lib.bm25_term_masks(self._h, _ptr(mu), mu.shape[1], _ptr(an), an.shape[1], _ptr(mn),
-                                  mn.shape[1], M, _ptr(b) if Mb else None, Mb, _ptr(out)))
+        if mm is None:
+            check(lib.bm25_term_masks(self._h, _ptr(mu), mu.shape[1], _ptr(an), an.shape[1],
+                                      _ptr(mn), mn.shape[1], M, _ptr(b) if Mb else None, Mb,
+                                      _ptr(out)))
+        else:
+            check(lib.bm25_term_masks_min_match(
+                self._h, _ptr(mu), mu.shape[1], _ptr(an), an.shape[1], _ptr(mn), mn.shape[1],
+                _ptr(mm), M, _ptr(b) if Mb else None, Mb, _ptr(out)))
         return out
 
-    def term_masks_device(self, d_must, d_any, d_must_not, d_base, d_out, stream=None) -> None:
+    def term_masks_device(self, d_must, d_any, d_must_not, d_base, d_out, stream=None, *,
+                          d_min_match=None) -> None:
         """Device-resident term_masks (bm25_term_masks_device): torch int32
         [M, width] clause tensors (or None: an empty clause), packed base
         masks [1 or M, W] (or None) in, packed masks d_out [M, W] (32-bit
         words) out, enqueued on ``stream`` with no host synchronisation and no
         validation of ids — an id >= n_terms is a term that no document has.
         Reads the index arrays only, so it may overlap a search of the same
-        handle on another stream."""
+        handle on another stream.  d_min_match: int32 [M] on the device
+        (bm25_term_masks_min_match_device; entries <= 0: the any clause is
+        optional)."""
         W = (self.n_docs + 31) // 32
         if d_out.dim() != 2 or d_out.shape[1] != W or d_out.element_size() != 4:
             raise ValueError(f"d_out must be a packed [M, {W}] tensor of 32-bit words")
         M = d_out.shape[0]
+        if d_min_match is not None and (d_min_match.dim() != 1 or d_min_match.shape[0] != M
+                                        or d_min_match.element_size() != 4
+                                        or d_min_match.is_floating_point()):
+            raise ValueError(f"d_min_match must be an int32 [{M}] tensor (one entry per mask)")
         args = []
         for name, c in (("d_must", d_must), ("d_any", d_any), ("d_must_not", d_must_not)):
             if c is None:
@@ -734,29 +785,75 @@ class GpuIndex:
             if Mb not in (1, M):
                 raise ValueError(f"d_base has {Mb} rows, expected 1 or {M}")
         s = getattr(stream, "cuda_stream", stream) or 0
-        check(lib.bm25_term_masks_device(
-            self._h, *args, M, ctypes.c_void_p(d_base.data_ptr()) if Mb else None, Mb,
-            ctypes.c_void_p(d_out.data_ptr()), ctypes.c_void_p(s)))
+        if d_min_match is None:
+            check(lib.bm25_term_masks_device(
+                self._h, *args, M, ctypes.c_void_p(d_base.data_ptr()) if Mb else None, Mb,
+                ctypes.c_void_p(d_out.data_ptr()), ctypes.c_void_p(s)))
+        else:
+            check(lib.bm25_term_masks_min_match_device(
+                self._h, *args, ctypes.c_void_p(d_min_match.data_ptr()) if M else None, M,
+                ctypes.c_void_p(d_base.data_ptr()) if Mb else None, Mb,
+                ctypes.c_void_p(d_out.data_ptr()), ctypes.c_void_p(s)))
+
+    def mask_count(self, masks) -> np.ndarray:
+        """The number of documents every mask allows (bm25_mask_count, host
+        arrays) -> int64 [M]: the set bits of each row among this handle's
+        n_docs documents (bits past n_docs of a packed row are ignored).
+        masks as search_filtered takes them: bool or packed uint32 rows."""
+        m = self._masks_arg(masks)
+        out = np.zeros(m.shape[0], np.int64)
+        check(lib.bm25_mask_count(self._h, _ptr(m) if m.size else None, m.shape[0], _ptr(out)))
+        return out
+
+    def mask_count_device(self, d_masks, d_counts, stream=None) -> None:
+        """Device-resident mask_count (bm25_mask_count_device): packed masks
+        [M, W] (32-bit words) in, int64 [M] counts out (they need not be
+        zeroed), enqueued on ``stream`` with no host synchronisation.  Reads
+        the masks only, so it may overlap a search of the same handle."""
+        W = (self.n_docs + 31) // 32
+        if d_masks.dim() != 2 or d_masks.shape[1] != W or d_masks.element_size() != 4:
+            raise ValueError(f"d_masks must be a packed [M, {W}] tensor of 32-bit words")
+        M = d_masks.shape[0]
+        if (d_counts.dim() != 1 or d_counts.shape[0] != M or d_counts.element_size() != 8
+                or d_counts.is_floating_point() or not d_counts.is_contiguous()):
+            raise ValueError(f"d_counts must be an int64 [{M}] tensor (one count per mask)")
+        if not d_masks.is_contiguous():
+            raise ValueError("d_masks must be contiguous")
+        s = getattr(stream, "cuda_stream", stream) or 0
+        check(lib.bm25_mask_count_device(
+            self._h, ctypes.c_void_p(d_masks.data_ptr()) if M and W else None, M,
+            ctypes.c_void_p(d_counts.data_ptr()) if M else None, ctypes.c_void_p(s)))
 
     def search_boolean(self, queries: np.ndarray, k: int, must=None, any=None, must_not=None,
-                       base=None) -> Tuple[np.ndarray, np.ndarray]:
+                       base=None, *, min_match=None, total_hits: bool = False):
         """Top-k of every query among the documents its clause row lets
         through (bm25_search_boolean, host arrays): search_filtered under
         term_masks(must, any, must_not, base) with one mask per query, the
         masks built on the device and never moved to the host.  Clauses and
-        base as term_masks, with one row per query (base: 1 row or Q)."""
+        base as term_masks, with one row per query (base: 1 row or Q).
+        min_match as term_masks'; total_hits=True returns (docs, scores,
+        totals), totals int64 [Q] = the documents each query's mask allows
+        (bm25_search_boolean_min_match; k = 0 then gives the totals alone)."""
         q = np.ascontiguousarray(queries, dtype=np.int32)
         if q.ndim != 2:
             raise ValueError("queries must be a 2-D [Q, T] int32 array")
         Q, T = q.shape
         mu, an, mn, _, b, Mb = self._clauses_arg(must, any, must_not, base, rows=Q)
+        mm = None if min_match is None else min_match_rows(an, min_match, "query")
         k = int(k)
         docs = np.zeros((Q, max(k, 0)), np.int32)
         scores = np.zeros((Q, max(k, 0)), np.float32)
-        check(lib.bm25_search_boolean(self._h, _ptr(q), Q, T, k, _ptr(mu), mu.shape[1], _ptr(an),
-                                      an.shape[1], _ptr(mn), mn.shape[1],
-                                      _ptr(b) if Mb else None, Mb, _ptr(docs), _ptr(scores)))
-        return docs, scores
+        if mm is None and not total_hits:
+            check(lib.bm25_search_boolean(self._h, _ptr(q), Q, T, k, _ptr(mu), mu.shape[1],
+                                          _ptr(an), an.shape[1], _ptr(mn), mn.shape[1],
+                                          _ptr(b) if Mb else None, Mb, _ptr(docs), _ptr(scores)))
+            return docs, scores
+        totals = np.zeros(Q, np.int64) if total_hits else None
+        check(lib.bm25_search_boolean_min_match(
+            self._h, _ptr(q), Q, T, k, _ptr(mu), mu.shape[1], _ptr(an), an.shape[1], _ptr(mn),
+            mn.shape[1], _ptr(mm), _ptr(b) if Mb else None, Mb, _ptr(docs), _ptr(scores),
+            _ptr(totals)))
+        return (docs, scores, totals) if total_hits else (docs, scores)
 
     # ------------------------------------------- bm25.BM25's float64 path
     def set_values_f64(self, data64) -> None:

@@ -1144,6 +1144,20 @@ int check_clause_ids(const bm25_index* h, int64_t mx, const int32_t* must, int64
   return check_token_ids(h->ix.n_terms, mx, must_not, M * N);
 }
 
+// min_match of the min-match calls (NULL: every row needs one term): the
+// clause width the counter holds — a shape, so the device call checks it too
+// — and, of host values, their sign.
+int check_min_match(const int32_t* min_match, int64_t B, int64_t M, bool host) {
+  if (!min_match) return BM25_OK;
+  if (B > 65535)
+    return fail(BM25_EINVAL, "min_match: the any clause holds B = %lld slots, at most 65535",
+                (long long)B);
+  for (int64_t m = 0; host && m < M; ++m)
+    if (min_match[m] < 0)
+      return fail(BM25_EINVAL, "min_match[%lld] = %d is negative", (long long)m, min_match[m]);
+  return BM25_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1151,8 +1165,17 @@ extern "C" {
 int bm25_term_masks(bm25_index* h, const int32_t* must, int64_t A, const int32_t* any, int64_t B,
                     const int32_t* must_not, int64_t N, int64_t M, const uint32_t* base, int64_t Mb,
                     uint32_t* out_masks) {
+  return bm25_term_masks_min_match(h, must, A, any, B, must_not, N, nullptr, M, base, Mb, out_masks);
+}
+
+int bm25_term_masks_min_match(bm25_index* h, const int32_t* must, int64_t A, const int32_t* any,
+                              int64_t B, const int32_t* must_not, int64_t N,
+                              const int32_t* min_match, int64_t M, const uint32_t* base, int64_t Mb,
+                              uint32_t* out_masks) {
   if (!h) return fail(BM25_EINVAL, "NULL index");
   int rc = check_clauses(must, A, any, B, must_not, N, M, base, Mb);
+  if (rc) return rc;
+  rc = check_min_match(min_match, B, M, true);
   if (rc) return rc;
   const int64_t W = (h->ix.n_docs + 31) >> 5;
   if (M == 0 || W == 0) return BM25_OK;
@@ -1167,9 +1190,11 @@ int bm25_term_masks(bm25_index* h, const int32_t* must, int64_t A, const int32_t
   const int32_t* d_any = c.upload(any, M * B);
   const int32_t* d_not = c.upload(must_not, M * N);
   const uint32_t* d_base = c.upload(base, Mb * W);
+  const int32_t* d_mm = c.upload(min_match, min_match ? M : 0);
   uint32_t* d_out = c.alloc<uint32_t>(M * W);
   if (c.ok())
-    c.run(launch_term_masks(h->ix, d_must, A, d_any, B, d_not, N, M, d_base, Mb, d_out, h->stream));
+    c.run(launch_term_masks(h->ix, d_must, A, d_any, B, d_not, N, M, d_base, Mb, d_out, h->stream,
+                            d_mm));
   c.download(out_masks, d_out, M * W);
   return c.finish("term_masks");
 }
@@ -1177,8 +1202,19 @@ int bm25_term_masks(bm25_index* h, const int32_t* must, int64_t A, const int32_t
 int bm25_term_masks_device(bm25_index* h, const int32_t* d_must, int64_t A, const int32_t* d_any,
                            int64_t B, const int32_t* d_must_not, int64_t N, int64_t M,
                            const uint32_t* d_base, int64_t Mb, uint32_t* d_out_masks, void* stream) {
+  return bm25_term_masks_min_match_device(h, d_must, A, d_any, B, d_must_not, N, nullptr, M, d_base,
+                                          Mb, d_out_masks, stream);
+}
+
+int bm25_term_masks_min_match_device(bm25_index* h, const int32_t* d_must, int64_t A,
+                                     const int32_t* d_any, int64_t B, const int32_t* d_must_not,
+                                     int64_t N, const int32_t* d_min_match, int64_t M,
+                                     const uint32_t* d_base, int64_t Mb, uint32_t* d_out_masks,
+                                     void* stream) {
   if (!h) return fail(BM25_EINVAL, "NULL index");
-  const int rc = check_clauses(d_must, A, d_any, B, d_must_not, N, M, d_base, Mb);
+  int rc = check_clauses(d_must, A, d_any, B, d_must_not, N, M, d_base, Mb);
+  if (rc) return rc;
+  rc = check_min_match(d_min_match, B, M, false);
   if (rc) return rc;
   if (M == 0 || h->ix.n_docs == 0) return BM25_OK;
   if (!d_out_masks) return fail(BM25_EINVAL, "NULL output");
@@ -1187,8 +1223,39 @@ int bm25_term_masks_device(bm25_index* h, const int32_t* d_must, int64_t A, cons
   Enter in(h);
   if (in.rc) return in.rc;
   HIP_TRY(launch_term_masks(h->ix, d_must, A, d_any, B, d_must_not, N, M, d_base, Mb, d_out_masks,
-                            (hipStream_t)stream),
+                            (hipStream_t)stream, d_min_match),
           "term_masks launch");
+  return BM25_OK;
+}
+
+int bm25_mask_count(bm25_index* h, const uint32_t* masks, int64_t M, int64_t* out_counts) {
+  if (!h) return fail(BM25_EINVAL, "NULL index");
+  if (M < 0) return fail(BM25_EINVAL, "negative mask shape");
+  if (M == 0) return BM25_OK;
+  if (!out_counts) return fail(BM25_EINVAL, "NULL output");
+  const int64_t W = (h->ix.n_docs + 31) >> 5;
+  if (W > 0 && !masks) return fail(BM25_EINVAL, "NULL masks");
+  Enter in(h);
+  if (in.rc) return in.rc;
+  HostCall c(h->stream);
+  const uint32_t* d_masks = c.upload(masks, M * W);
+  int64_t* d_counts = c.alloc<int64_t>(M);
+  if (c.ok()) c.run(launch_mask_count(h->ix, d_masks, M, d_counts, h->stream));
+  c.download(out_counts, d_counts, M);
+  return c.finish("mask_count");
+}
+
+int bm25_mask_count_device(bm25_index* h, const uint32_t* d_masks, int64_t M, int64_t* d_counts,
+                           void* stream) {
+  if (!h) return fail(BM25_EINVAL, "NULL index");
+  if (M < 0) return fail(BM25_EINVAL, "negative mask shape");
+  if (M == 0) return BM25_OK;
+  if (!d_counts) return fail(BM25_EINVAL, "NULL output");
+  if (h->ix.n_docs > 0 && !d_masks) return fail(BM25_EINVAL, "NULL masks");
+  // reads the caller's masks only (as bm25_term_masks_device: no workspace)
+  Enter in(h);
+  if (in.rc) return in.rc;
+  HIP_TRY(launch_mask_count(h->ix, d_masks, M, d_counts, (hipStream_t)stream), "mask_count launch");
   return BM25_OK;
 }
 
@@ -1196,24 +1263,42 @@ int bm25_search_boolean(bm25_index* h, const int32_t* queries, int64_t Q, int64_
                         const int32_t* must, int64_t A, const int32_t* any, int64_t B,
                         const int32_t* must_not, int64_t N, const uint32_t* base, int64_t Mb,
                         int32_t* out_docs, float* out_scores) {
+  return bm25_search_boolean_min_match(h, queries, Q, T, k, must, A, any, B, must_not, N, nullptr,
+                                       base, Mb, out_docs, out_scores, nullptr);
+}
+
+int bm25_search_boolean_min_match(bm25_index* h, const int32_t* queries, int64_t Q, int64_t T,
+                                  int32_t k, const int32_t* must, int64_t A, const int32_t* any,
+                                  int64_t B, const int32_t* must_not, int64_t N,
+                                  const int32_t* min_match, const uint32_t* base, int64_t Mb,
+                                  int32_t* out_docs, float* out_scores, int64_t* out_total_hits) {
   if (!h) return fail(BM25_EINVAL, "NULL index");
   if (Q < 0 || T < 0) return fail(BM25_EINVAL, "negative query shape");
   int rc = check_clauses(must, A, any, B, must_not, N, Q, base, Mb);
   if (rc) return rc;
+  rc = check_min_match(min_match, B, Q, true);
+  if (rc) return rc;
   rc = check_k(h, k);
   if (rc) return rc;
-  if (Q == 0 || k == 0) return BM25_OK;
-  if (T > 0 && !queries) return fail(BM25_EINVAL, "NULL queries");
-  if (!out_docs || !out_scores) return fail(BM25_EINVAL, "NULL output");
-  rc = check_clause_ids(h, max_token(0, queries, Q * T), must, A, any, B, must_not, N, Q);
+  // (k == 0 with out_total_hits: "how many match" alone — the masks are still
+  // built and counted)
+  if (Q == 0 || (k == 0 && !out_total_hits)) return BM25_OK;
+  if (k > 0 && T > 0 && !queries) return fail(BM25_EINVAL, "NULL queries");
+  if (k > 0 && (!out_docs || !out_scores)) return fail(BM25_EINVAL, "NULL output");
+  rc = check_clause_ids(h, max_token(0, queries, k > 0 ? Q * T : 0), must, A, any, B, must_not, N,
+                        Q);
   if (rc) return rc;
   Enter in(h);
   if (in.rc) return in.rc;
-  rc = ensure_io(h, Q * T, Q * (int64_t)k);
+  rc = ensure_io(h, k > 0 ? Q * T : 0, Q * (int64_t)k);
   if (rc) return rc;
   // queries per chunk: the masks of one chunk stay on the device, in a buffer
   // of this call's own of at most 1 GiB (automatic) and at least one query
-  const int64_t W = (h->ix.n_docs + 31) >> 5;  // (k >= 1: n_docs >= 1)
+  const int64_t W = (h->ix.n_docs + 31) >> 5;
+  if (W == 0) {  // (k == 0: an index without documents matches none)
+    std::fill(out_total_hits, out_total_hits + Q, (int64_t)0);
+    return BM25_OK;
+  }
   int64_t chunk = h->ix.opt.bool_chunk > 0 ? h->ix.opt.bool_chunk
                                            : std::max<int64_t>(1, ((int64_t)1 << 28) / W);
   chunk = std::min(chunk, Q);
@@ -1224,24 +1309,31 @@ int bm25_search_boolean(bm25_index* h, const int32_t* queries, int64_t Q, int64_
   const int32_t* d_any = c.upload(any, Q * B);
   const int32_t* d_not = c.upload(must_not, Q * N);
   const uint32_t* d_base = c.upload(base, Mb * W);
+  const int32_t* d_mm = c.upload(min_match, min_match ? Q : 0);
+  int64_t* d_hits = out_total_hits ? c.alloc<int64_t>(Q) : nullptr;
   uint32_t* d_masks = c.alloc<uint32_t>(chunk * W);
   int32_t* d_qm = c.alloc<int32_t>(chunk);
   c.upload_to(d_qm, ids.data(), chunk);
-  c.upload_to(h->d_q, queries, Q * T);
+  if (k > 0) c.upload_to(h->d_q, queries, Q * T);
   int64_t n_dense = 0;
   for (int64_t q0 = 0; c.ok() && q0 < Q; q0 += chunk) {
     const int64_t n = std::min(chunk, Q - q0);
     c.run(launch_term_masks(h->ix, d_must + q0 * A, A, d_any + q0 * B, B, d_not + q0 * N, N, n,
                             Mb == Q && Q > 1 ? d_base + q0 * W : d_base,
-                            Mb == 0 ? 0 : (Mb == 1 ? 1 : n), d_masks, h->stream));
+                            Mb == 0 ? 0 : (Mb == 1 ? 1 : n), d_masks, h->stream,
+                            d_mm ? d_mm + q0 : nullptr));
+    // the chunk's counts, before its mask buffer is reused
+    if (d_hits && c.ok()) c.run(launch_mask_count(h->ix, d_masks, n, d_hits + q0, h->stream));
     if (!c.ok()) break;
+    if (k == 0) continue;  // (the counts alone: no search ran, the handle's counters stay)
     c.hold(run_filtered(h, h->d_q + q0 * T, n, T, k, d_masks, n, d_qm, h->d_docs + q0 * k,
                         h->d_scores + q0 * k, h->stream));
     n_dense += h->filtered_dense;
   }
-  h->filtered_dense = n_dense;
+  if (k > 0) h->filtered_dense = n_dense;
   c.download(out_docs, h->d_docs, Q * k);
   c.download(out_scores, h->d_scores, Q * k);
+  if (d_hits) c.download(out_total_hits, d_hits, Q);
   return c.finish("boolean search");
 }
 

@@ -532,10 +532,19 @@ hipError_t launch_search_filtered(const DevIndex& ix, const int32_t* d_queries, 
 // padding, an id >= n_terms is a term that no document has.  Every word of
 // every row is written (bits at or past n_docs as 0), no word at index >= W
 // is read or written.  Reads the index arrays only (no workspace).
+// d_min_match [M] (null: the kernel of the calls without it): row m's any
+// clause asks for d_min_match[m] of its slots with an id >= 0 — a repeated id
+// counts each time — and for nothing where that is <= 0; B <= 65535 then.
 hipError_t launch_term_masks(const DevIndex& ix, const int32_t* d_must, int64_t A,
                              const int32_t* d_any, int64_t B, const int32_t* d_must_not, int64_t N,
                              int64_t M, const uint32_t* d_base, int64_t Mb, uint32_t* d_out,
-                             hipStream_t stream);
+                             hipStream_t stream, const int32_t* d_min_match = nullptr);
+
+// d_counts[m] = the set bits of d_masks[m][W] among bits 0 .. n_docs - 1 (the
+// bits at or past n_docs of the last word are ignored).  d_counts need not be
+// zeroed; integer sums, so the result does not depend on scheduling.
+hipError_t launch_mask_count(const DevIndex& ix, const uint32_t* d_masks, int64_t M,
+                             int64_t* d_counts, hipStream_t stream);
 
 // Largest token id of [n] device ids (0 if none is positive) into *d_out.
 hipError_t launch_max_token(const int32_t* d_queries, int64_t n, int32_t* d_out,
