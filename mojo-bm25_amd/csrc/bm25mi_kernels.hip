@@ -4224,7 +4224,9 @@ hipError_t launch_score(const DevIndex& ix, const int32_t* d_queries, int64_t Q,
   // (shard_geom_world: its own geometry where the world's tile bounds do not
   // serve — the shard's own k-th key is a valid, looser threshold)
   const SampleGeom g = shard_geom_world(ix, k, T, world);
-  world = world && g.P == 0;
+  // ... and then reads its own tables: g.P == 0 alone does not say whose bounds serve (a
+  // collection of more than kBoundMaxTiles tiles over shards that each stay below it)
+  world = world && search_geom(ix, ix.wtiles, k, 1, T).P == 0;
   const int64_t ntg = world ? ix.wtiles : ix.ntiles;
   // split REST items where the waves get few items each (a doc shard of a
   // few GPUs' collection: ~16 at W = 8): the heavy queries' last items set
