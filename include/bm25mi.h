@@ -596,6 +596,60 @@ int bm25_search_boolean_min_match(bm25_index* idx, const int32_t* queries, int64
                                   int32_t* out_docs, float* out_scores, int64_t* out_total_hits);
 
 /*
+ * Facet counts: the hit count of every allow-mask broken down by a
+ * per-document field (a "terms aggregation": how many match per language,
+ * tenant, year or source), on the device.  Replaces no reference call.
+ *   groups [n_docs] int32: groups[d] = the group (category id) of handle-local
+ *              document d, in [0, G); a negative value = the document has no group.
+ *   masks  [M, W] uint32, W = ceil(n_docs / 32), the layout of bm25_search_filtered.
+ *   out    [M, G] int64, rows contiguous:
+ *     out[m][g] = number of d in [0, n_docs) with bit d of mask row m set and groups[d] == g
+ *   Every entry of out is written; the caller need not zero it.  Bits at or
+ *   past n_docs in the last word are ignored even when set.  No mask word at
+ *   index >= W of a row is read, no entry of groups at index >= n_docs is
+ *   read, nothing past M * G counts is written.  M may pass 65535; G == 0 or
+ *   M == 0 returns BM25_OK without device work; G lies in [0, 2^31 - 1].  The
+ *   sums are integer, so the result does not depend on scheduling.
+ *   Identity: sum_g out[m][g] + (allowed documents of row m with a negative
+ *   group) == bm25_mask_count of row m.  On doc shards the bits and the groups
+ *   are by the handle's own documents, so the shards' [M, G] outputs add up
+ *   element-wise to the collection's.
+ *   The facet calls are not searches: they leave bm25_search_dispatch,
+ *   bm25_search_counters and bm25_search_filtered_stats alone.
+ *   bm25_mask_facets: host buffers, validated, synchronous.  BM25_EINVAL for
+ *     a NULL index, a negative M or G (or G > 2^31 - 1), a NULL pointer with a
+ *     non-empty shape, and a groups[d] >= G (the message names d and the
+ *     value).  On any error the outputs are untouched.
+ *   bm25_mask_facets_device: device buffers, enqueued on `stream`; checks
+ *     shapes and NULL pointers only, never synchronises, retains no scratch,
+ *     reads the caller's masks and groups only (no workspace, no index array)
+ *     and is not ordered against the handle's searches: it may run on its own
+ *     stream while a search of the same handle is in flight, as
+ *     bm25_mask_count_device may.  A groups[d] >= G counts nowhere, exactly
+ *     like a negative value; nothing outside the caller's buffers is touched.
+ *   bm25_search_boolean_facets: bm25_search_boolean_min_match plus the
+ *     per-query facet rows, out_facets [Q, G] int64 = the facet counts of each
+ *     query's mask.  The groups (validated as bm25_mask_facets validates them)
+ *     are uploaded once per call; each chunk's facets are taken on the device
+ *     where its hit counts are taken, before its mask buffer is reused, so the
+ *     masks still never move to the host.  k == 0 with a non-NULL out_facets or
+ *     out_total_hits builds the masks and counts alone (queries, out_docs and
+ *     out_scores may then be NULL).  With groups NULL and out_facets NULL every
+ *     output equals bm25_search_boolean_min_match's, which is this call
+ *     without them; exactly one of the two with G > 0 is BM25_EINVAL.
+ */
+int bm25_mask_facets(bm25_index* idx, const uint32_t* masks, int64_t M, const int32_t* groups,
+                     int64_t G, int64_t* out_counts);
+int bm25_mask_facets_device(bm25_index* idx, const uint32_t* d_masks, int64_t M,
+                            const int32_t* d_groups, int64_t G, int64_t* d_counts, void* stream);
+int bm25_search_boolean_facets(bm25_index* idx, const int32_t* queries, int64_t Q, int64_t T,
+                               int32_t k, const int32_t* must, int64_t A, const int32_t* any,
+                               int64_t B, const int32_t* must_not, int64_t N,
+                               const int32_t* min_match, const uint32_t* base, int64_t Mb,
+                               const int32_t* groups, int64_t G, int32_t* out_docs,
+                               float* out_scores, int64_t* out_total_hits, int64_t* out_facets);
+
+/*
  * bm25.BM25's float64 path (the dense model's API keeps the reference's
  * precision).  bm25_index_set_values_f64 keeps a float64 copy of the index's
  * values beside it (the same CSC order; bm25_build_scores method 1 returns

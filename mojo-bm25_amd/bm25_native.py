@@ -237,7 +237,7 @@ class BM25v:
         return self._gpu.search_after(queries, top_k, after, weights, allow, qm)
 
     def search_boolean(self, queries, top_k: int, must=None, any=None, must_not=None,
-                       base=None, *, min_match=None, total_hits: bool = False):
+                       base=None, *, min_match=None, total_hits: bool = False, facets=None):
         """search under boolean term filters (not in the reference, whose
         search has no term filter): query q ranks only the documents that hold
         every term of ``must[q]``, at least one of ``any[q]`` (when it names
@@ -250,10 +250,19 @@ class BM25v:
         bm25mi.min_match_rows; 0: the clause is optional).  Returns
         search_filtered's tuple, with ``total_hits=True`` followed by the
         int64 [Q] number of documents each query's filter lets through; the
-        masks are built and counted on the GPU."""
+        masks are built and counted on the GPU.  ``facets=(groups, n_groups)``
+        (groups: an integer group id per document, negative = none, as
+        bm25mi.facet_codes makes them of labels) appends, as the last element,
+        the int64 [Q, n_groups] count of those documents per group."""
+        if facets is not None and (not isinstance(facets, (tuple, list)) or len(facets) != 2):
+            raise ValueError("facets must be a pair (groups, n_groups)")
         if len(queries) == 0:
             empty = np.zeros((0, 0), dtype=self.dtype), np.zeros((0, 0), dtype=self.dtype)
-            return empty + (np.zeros(0, np.int64),) if total_hits else empty
+            if total_hits:
+                empty += (np.zeros(0, np.int64),)
+            if facets is not None:
+                empty += (np.zeros((0, max(int(facets[1]), 0)), np.int64),)
+            return empty
         if (not isinstance(queries, np.ndarray) or queries.ndim != 2
                 or not isinstance(queries[0][0], TokId)):
             raise ValueError("The queries must be a list of list of query token IDs.")
@@ -284,8 +293,11 @@ class BM25v:
                 "of tokens in the index.")
         if self._gpu is None:
             raise ValueError("BM25v index not built. Call index() first.")
+        if facets is None:
+            return self._gpu.search_boolean(queries, top_k, clauses[0], clauses[1], clauses[2],
+                                            base, min_match=min_match, total_hits=total_hits)
         return self._gpu.search_boolean(queries, top_k, clauses[0], clauses[1], clauses[2], base,
-                                        min_match=min_match, total_hits=total_hits)
+                                        min_match=min_match, total_hits=total_hits, facets=facets)
 
     def _compute_relevance_from_scores(self, queries, top_k: int, dtype=np.float32):
         """bm25_native.py:129-158 on the GPU: per query, negative ids dropped,

@@ -92,6 +92,50 @@ def min_match_rows(any_rows, spec, what: str = "mask") -> np.ndarray:
     return np.ascontiguousarray(mm, dtype=np.int32)
 
 
+def facet_codes(labels):
+    """Arbitrary per-document labels -> (codes int32 [n], uniques): the group
+    ids the facet counts take, with np.unique(..., return_inverse=True)
+    semantics — uniques sorted, uniques[codes[d]] == labels[d] — except that a
+    None or masked entry has no group: its code is -1 and it is no unique."""
+    if isinstance(labels, np.ma.MaskedArray):
+        missing = np.ma.getmaskarray(labels).ravel()
+        a = np.ma.getdata(labels).ravel()
+    else:
+        a = np.asarray(labels).ravel()
+        missing = np.zeros(a.size, bool)
+    if a.dtype == object:
+        missing = missing | np.fromiter((x is None for x in a), bool, a.size)
+    present = a[~missing]
+    if a.dtype == object and present.size:
+        present = np.asarray(list(present))  # (strings, ints: numpy's own dtype)
+    uniques, inverse = np.unique(present, return_inverse=True)
+    if uniques.size > np.iinfo(np.int32).max:
+        raise ValueError("more distinct labels than an int32 group id holds")
+    codes = np.full(a.size, -1, np.int32)
+    codes[~missing] = inverse.ravel()
+    return codes, uniques
+
+
+def _facet_groups(groups, n_groups, n_docs: int):
+    """The (groups, n_groups) of the facet calls -> (int32 [n_docs], G);
+    shape and dtype errors are raised here, before any C call."""
+    if isinstance(n_groups, (bool, np.bool_)) or not isinstance(n_groups, (int, np.integer)):
+        raise ValueError("n_groups must be an int")
+    G = int(n_groups)
+    if G < 0:
+        raise ValueError(f"n_groups = {G} is negative")
+    if G > np.iinfo(np.int32).max:
+        raise ValueError("n_groups must fit int32 (a group id is an int32)")
+    g = np.asarray(groups)
+    if g.dtype.kind not in "iu":
+        raise ValueError("groups must be an integer array (bm25mi.facet_codes makes one of labels)")
+    if g.ndim != 1 or g.shape[0] != n_docs:
+        raise ValueError(f"groups has shape {g.shape}, expected ({n_docs},) (one per document)")
+    if g.size and (int(g.max()) > np.iinfo(np.int32).max or int(g.min()) < np.iinfo(np.int32).min):
+        raise ValueError("groups entries must fit int32")
+    return np.ascontiguousarray(g, dtype=np.int32), G
+
+
 AFTER_NONE = -2  # BM25_AFTER_NONE: an after-docs entry that means "no cursor"
 
 
@@ -824,8 +868,53 @@ class GpuIndex:
             self._h, ctypes.c_void_p(d_masks.data_ptr()) if M and W else None, M,
             ctypes.c_void_p(d_counts.data_ptr()) if M else None, ctypes.c_void_p(s)))
 
+    def facets(self, masks, groups, n_groups) -> np.ndarray:
+        """Facet counts (bm25_mask_facets, host arrays) -> int64 [M, G]:
+        out[m][g] = the documents of this handle that mask m allows and whose
+        group is g.  masks as mask_count takes them; groups: any integer array
+        of n_docs entries (group ids in [0, n_groups); negative: the document
+        has no group; bm25mi.facet_codes turns labels into ids), converted to
+        contiguous int32.  A group id >= n_groups is a ValueError."""
+        m = self._masks_arg(masks)
+        g, G = _facet_groups(groups, n_groups, self.n_docs)
+        out = np.zeros((m.shape[0], G), np.int64)
+        check(lib.bm25_mask_facets(self._h, _ptr(m) if m.size else None, m.shape[0],
+                                   _ptr(g) if g.size else None, G, _ptr(out) if out.size else None))
+        return out
+
+    def facets_device(self, d_masks, d_groups, n_groups, d_counts, stream=None) -> None:
+        """Device-resident facets (bm25_mask_facets_device): packed masks
+        [M, W] (32-bit words) and int32 groups [n_docs] in, int64 [M, G]
+        counts out (they need not be zeroed), enqueued on ``stream`` with no
+        host synchronisation.  A group id outside [0, n_groups) counts nowhere.
+        Reads the masks and groups only, so it may overlap a search of the
+        same handle."""
+        W = (self.n_docs + 31) // 32
+        if d_masks.dim() != 2 or d_masks.shape[1] != W or d_masks.element_size() != 4:
+            raise ValueError(f"d_masks must be a packed [M, {W}] tensor of 32-bit words")
+        M = d_masks.shape[0]
+        if isinstance(n_groups, bool) or not isinstance(n_groups, (int, np.integer)):
+            raise ValueError("n_groups must be an int")
+        G = int(n_groups)
+        if G < 0 or G > np.iinfo(np.int32).max:
+            raise ValueError(f"n_groups = {G} must be in 0 .. 2^31 - 1")
+        if (d_groups.dim() != 1 or d_groups.shape[0] != self.n_docs or d_groups.element_size() != 4
+                or d_groups.is_floating_point() or not d_groups.is_contiguous()):
+            raise ValueError(f"d_groups must be an int32 [{self.n_docs}] tensor (one group per "
+                             "document)")
+        if (d_counts.dim() != 2 or tuple(d_counts.shape) != (M, G) or d_counts.element_size() != 8
+                or d_counts.is_floating_point() or not d_counts.is_contiguous()):
+            raise ValueError(f"d_counts must be an int64 [{M}, {G}] tensor (one row per mask)")
+        if not d_masks.is_contiguous():
+            raise ValueError("d_masks must be contiguous")
+        s = getattr(stream, "cuda_stream", stream) or 0
+        check(lib.bm25_mask_facets_device(
+            self._h, ctypes.c_void_p(d_masks.data_ptr()) if M and W else None, M,
+            ctypes.c_void_p(d_groups.data_ptr()) if self.n_docs else None, G,
+            ctypes.c_void_p(d_counts.data_ptr()) if M and G else None, ctypes.c_void_p(s)))
+
     def search_boolean(self, queries: np.ndarray, k: int, must=None, any=None, must_not=None,
-                       base=None, *, min_match=None, total_hits: bool = False):
+                       base=None, *, min_match=None, total_hits: bool = False, facets=None):
         """Top-k of every query among the documents its clause row lets
         through (bm25_search_boolean, host arrays): search_filtered under
         term_masks(must, any, must_not, base) with one mask per query, the
@@ -833,16 +922,33 @@ class GpuIndex:
         base as term_masks, with one row per query (base: 1 row or Q).
         min_match as term_masks'; total_hits=True returns (docs, scores,
         totals), totals int64 [Q] = the documents each query's mask allows
-        (bm25_search_boolean_min_match; k = 0 then gives the totals alone)."""
+        (bm25_search_boolean_min_match; k = 0 then gives the totals alone).
+        facets=(groups, n_groups), as GpuIndex.facets takes them, appends the
+        int64 [Q, n_groups] facet counts of each query's mask as the last
+        element of the tuple (bm25_search_boolean_facets)."""
         q = np.ascontiguousarray(queries, dtype=np.int32)
         if q.ndim != 2:
             raise ValueError("queries must be a 2-D [Q, T] int32 array")
         Q, T = q.shape
         mu, an, mn, _, b, Mb = self._clauses_arg(must, any, must_not, base, rows=Q)
         mm = None if min_match is None else min_match_rows(an, min_match, "query")
+        if facets is not None:
+            if not isinstance(facets, (tuple, list)) or len(facets) != 2:
+                raise ValueError("facets must be a pair (groups, n_groups)")
+            fg, G = _facet_groups(facets[0], facets[1], self.n_docs)
         k = int(k)
         docs = np.zeros((Q, max(k, 0)), np.int32)
         scores = np.zeros((Q, max(k, 0)), np.float32)
+        if facets is not None:
+            totals = np.zeros(Q, np.int64) if total_hits else None
+            counts = np.zeros((Q, G), np.int64)
+            give = bool(G and fg.size)  # (G == 0, or no document: all-zero rows, no pointer)
+            check(lib.bm25_search_boolean_facets(
+                self._h, _ptr(q), Q, T, k, _ptr(mu), mu.shape[1], _ptr(an), an.shape[1], _ptr(mn),
+                mn.shape[1], _ptr(mm), _ptr(b) if Mb else None, Mb, _ptr(fg) if give else None,
+                G if give else 0, _ptr(docs), _ptr(scores), _ptr(totals),
+                _ptr(counts) if give else None))
+            return (docs, scores, totals, counts) if total_hits else (docs, scores, counts)
         if mm is None and not total_hits:
             check(lib.bm25_search_boolean(self._h, _ptr(q), Q, T, k, _ptr(mu), mu.shape[1],
                                           _ptr(an), an.shape[1], _ptr(mn), mn.shape[1],

@@ -1158,6 +1158,23 @@ int check_min_match(const int32_t* min_match, int64_t B, int64_t M, bool host) {
   return BM25_OK;
 }
 
+// The facet arguments' shape, G in [0, 2^31 - 1]: a group id is an int32.
+int check_facet_shape(int64_t M, int64_t G) {
+  if (M < 0 || G < 0) return fail(BM25_EINVAL, "negative facet shape");
+  if (G > 0x7FFFFFFFll)
+    return fail(BM25_EINVAL, "G = %lld groups: at most 2^31 - 1", (long long)G);
+  return BM25_OK;
+}
+
+// Host group ids: an id >= G names no group (a negative one: no group at all).
+int check_groups(const int32_t* groups, int64_t n_docs, int64_t G) {
+  for (int64_t d = 0; d < n_docs; ++d)
+    if (groups[d] >= G)
+      return fail(BM25_EINVAL, "groups[%lld] = %d is not below G = %lld", (long long)d, groups[d],
+                  (long long)G);
+  return BM25_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1259,6 +1276,46 @@ int bm25_mask_count_device(bm25_index* h, const uint32_t* d_masks, int64_t M, in
   return BM25_OK;
 }
 
+int bm25_mask_facets(bm25_index* h, const uint32_t* masks, int64_t M, const int32_t* groups,
+                     int64_t G, int64_t* out_counts) {
+  if (!h) return fail(BM25_EINVAL, "NULL index");
+  int rc = check_facet_shape(M, G);
+  if (rc) return rc;
+  if (M == 0 || G == 0) return BM25_OK;
+  if (!out_counts) return fail(BM25_EINVAL, "NULL output");
+  const int64_t n_docs = h->ix.n_docs, W = (n_docs + 31) >> 5;
+  if (W > 0 && !masks) return fail(BM25_EINVAL, "NULL masks");
+  if (n_docs > 0 && !groups) return fail(BM25_EINVAL, "NULL groups");
+  rc = check_groups(groups, n_docs, G);
+  if (rc) return rc;
+  Enter in(h);
+  if (in.rc) return in.rc;
+  HostCall c(h->stream);
+  const uint32_t* d_masks = c.upload(masks, M * W);
+  const int32_t* d_groups = c.upload(groups, n_docs);
+  int64_t* d_counts = c.alloc<int64_t>(M * G);
+  if (c.ok()) c.run(launch_mask_facets(h->ix, d_masks, M, d_groups, G, d_counts, h->stream));
+  c.download(out_counts, d_counts, M * G);
+  return c.finish("mask_facets");
+}
+
+int bm25_mask_facets_device(bm25_index* h, const uint32_t* d_masks, int64_t M,
+                            const int32_t* d_groups, int64_t G, int64_t* d_counts, void* stream) {
+  if (!h) return fail(BM25_EINVAL, "NULL index");
+  const int rc = check_facet_shape(M, G);
+  if (rc) return rc;
+  if (M == 0 || G == 0) return BM25_OK;
+  if (!d_counts) return fail(BM25_EINVAL, "NULL output");
+  if (h->ix.n_docs > 0 && !d_masks) return fail(BM25_EINVAL, "NULL masks");
+  if (h->ix.n_docs > 0 && !d_groups) return fail(BM25_EINVAL, "NULL groups");
+  // reads the caller's masks and groups only (as bm25_mask_count_device: no workspace)
+  Enter in(h);
+  if (in.rc) return in.rc;
+  HIP_TRY(launch_mask_facets(h->ix, d_masks, M, d_groups, G, d_counts, (hipStream_t)stream),
+          "mask_facets launch");
+  return BM25_OK;
+}
+
 int bm25_search_boolean(bm25_index* h, const int32_t* queries, int64_t Q, int64_t T, int32_t k,
                         const int32_t* must, int64_t A, const int32_t* any, int64_t B,
                         const int32_t* must_not, int64_t N, const uint32_t* base, int64_t Mb,
@@ -1272,22 +1329,42 @@ int bm25_search_boolean_min_match(bm25_index* h, const int32_t* queries, int64_t
                                   int64_t B, const int32_t* must_not, int64_t N,
                                   const int32_t* min_match, const uint32_t* base, int64_t Mb,
                                   int32_t* out_docs, float* out_scores, int64_t* out_total_hits) {
+  return bm25_search_boolean_facets(h, queries, Q, T, k, must, A, any, B, must_not, N, min_match,
+                                    base, Mb, nullptr, 0, out_docs, out_scores, out_total_hits,
+                                    nullptr);
+}
+
+int bm25_search_boolean_facets(bm25_index* h, const int32_t* queries, int64_t Q, int64_t T,
+                               int32_t k, const int32_t* must, int64_t A, const int32_t* any,
+                               int64_t B, const int32_t* must_not, int64_t N,
+                               const int32_t* min_match, const uint32_t* base, int64_t Mb,
+                               const int32_t* groups, int64_t G, int32_t* out_docs,
+                               float* out_scores, int64_t* out_total_hits, int64_t* out_facets) {
   if (!h) return fail(BM25_EINVAL, "NULL index");
   if (Q < 0 || T < 0) return fail(BM25_EINVAL, "negative query shape");
   int rc = check_clauses(must, A, any, B, must_not, N, Q, base, Mb);
   if (rc) return rc;
   rc = check_min_match(min_match, B, Q, true);
   if (rc) return rc;
+  rc = check_facet_shape(Q, G);
+  if (rc) return rc;
+  if (G > 0 && (groups == nullptr) != (out_facets == nullptr))
+    return fail(BM25_EINVAL, "facets: groups and out_facets come together (one of them is NULL)");
+  if (G == 0 || !groups) out_facets = nullptr;  // (no group: no facet row to write)
   rc = check_k(h, k);
   if (rc) return rc;
-  // (k == 0 with out_total_hits: "how many match" alone — the masks are still
-  // built and counted)
-  if (Q == 0 || (k == 0 && !out_total_hits)) return BM25_OK;
+  // (k == 0 with out_total_hits or out_facets: "how many match" alone — the
+  // masks are still built and counted)
+  if (Q == 0 || (k == 0 && !out_total_hits && !out_facets)) return BM25_OK;
   if (k > 0 && T > 0 && !queries) return fail(BM25_EINVAL, "NULL queries");
   if (k > 0 && (!out_docs || !out_scores)) return fail(BM25_EINVAL, "NULL output");
   rc = check_clause_ids(h, max_token(0, queries, k > 0 ? Q * T : 0), must, A, any, B, must_not, N,
                         Q);
   if (rc) return rc;
+  if (out_facets) {
+    rc = check_groups(groups, h->ix.n_docs, G);
+    if (rc) return rc;
+  }
   Enter in(h);
   if (in.rc) return in.rc;
   rc = ensure_io(h, k > 0 ? Q * T : 0, Q * (int64_t)k);
@@ -1296,7 +1373,8 @@ int bm25_search_boolean_min_match(bm25_index* h, const int32_t* queries, int64_t
   // of this call's own of at most 1 GiB (automatic) and at least one query
   const int64_t W = (h->ix.n_docs + 31) >> 5;
   if (W == 0) {  // (k == 0: an index without documents matches none)
-    std::fill(out_total_hits, out_total_hits + Q, (int64_t)0);
+    if (out_total_hits) std::fill(out_total_hits, out_total_hits + Q, (int64_t)0);
+    if (out_facets) std::fill(out_facets, out_facets + Q * G, (int64_t)0);
     return BM25_OK;
   }
   int64_t chunk = h->ix.opt.bool_chunk > 0 ? h->ix.opt.bool_chunk
@@ -1311,6 +1389,9 @@ int bm25_search_boolean_min_match(bm25_index* h, const int32_t* queries, int64_t
   const uint32_t* d_base = c.upload(base, Mb * W);
   const int32_t* d_mm = c.upload(min_match, min_match ? Q : 0);
   int64_t* d_hits = out_total_hits ? c.alloc<int64_t>(Q) : nullptr;
+  // the groups go up once per call; every chunk's facet rows land in one [Q, G] buffer
+  const int32_t* d_groups = out_facets ? c.upload(groups, h->ix.n_docs) : nullptr;
+  int64_t* d_facets = out_facets ? c.alloc<int64_t>(Q * G) : nullptr;
   uint32_t* d_masks = c.alloc<uint32_t>(chunk * W);
   int32_t* d_qm = c.alloc<int32_t>(chunk);
   c.upload_to(d_qm, ids.data(), chunk);
@@ -1324,6 +1405,8 @@ int bm25_search_boolean_min_match(bm25_index* h, const int32_t* queries, int64_t
                             d_mm ? d_mm + q0 : nullptr));
     // the chunk's counts, before its mask buffer is reused
     if (d_hits && c.ok()) c.run(launch_mask_count(h->ix, d_masks, n, d_hits + q0, h->stream));
+    if (d_facets && c.ok())
+      c.run(launch_mask_facets(h->ix, d_masks, n, d_groups, G, d_facets + q0 * G, h->stream));
     if (!c.ok()) break;
     if (k == 0) continue;  // (the counts alone: no search ran, the handle's counters stay)
     c.hold(run_filtered(h, h->d_q + q0 * T, n, T, k, d_masks, n, d_qm, h->d_docs + q0 * k,
@@ -1334,6 +1417,7 @@ int bm25_search_boolean_min_match(bm25_index* h, const int32_t* queries, int64_t
   c.download(out_docs, h->d_docs, Q * k);
   c.download(out_scores, h->d_scores, Q * k);
   if (d_hits) c.download(out_total_hits, d_hits, Q);
+  if (d_facets) c.download(out_facets, d_facets, Q * G);
   return c.finish("boolean search");
 }
 

@@ -546,6 +546,27 @@ hipError_t launch_term_masks(const DevIndex& ix, const int32_t* d_must, int64_t 
 hipError_t launch_mask_count(const DevIndex& ix, const uint32_t* d_masks, int64_t M,
                              int64_t* d_counts, hipStream_t stream);
 
+// Facet counts (bm25mi_facets.hip): d_counts[m][g], [M, G] int64 with
+// contiguous rows, = the documents d < n_docs with bit d of d_masks[m][W] set
+// and d_groups[d] == g; a d_groups[d] outside [0, G) counts nowhere.  Every
+// entry is written (d_counts need not be zeroed), bits at or past n_docs of
+// the last word are ignored, no mask word at index >= W of a row and no
+// d_groups entry at index >= n_docs is read.  Integer sums.  G <= kFacetBins:
+// facet_rows(G) rows share one read of a chunk's groups, their bins in LDS;
+// wider G: a row per pass, global atomics.  facet_chunk_docs: the documents
+// of a workgroup's chunk on the route that (G, M) takes.
+constexpr int64_t kFacetBins = 8192;          // u32 LDS bins of a workgroup (32 KiB)
+constexpr int64_t kFacetMaxRows = 64;         // mask rows of a row block, at most
+constexpr int64_t kFacetMinChunk = 8192;      // documents of a chunk, LDS route: 8 per bin,
+constexpr int64_t kFacetMaxChunk = 65536;     //   within these,
+constexpr int64_t kFacetChunkStep = 1024;     //   rounded up to a multiple of this
+constexpr int64_t kFacetGlobalChunk = 16384;  // documents of a chunk, global route
+int64_t facet_rows(int64_t G);
+int64_t facet_chunk_docs(int64_t G, int64_t M);
+hipError_t launch_mask_facets(const DevIndex& ix, const uint32_t* d_masks, int64_t M,
+                              const int32_t* d_groups, int64_t G, int64_t* d_counts,
+                              hipStream_t stream);
+
 // Largest token id of [n] device ids (0 if none is positive) into *d_out.
 hipError_t launch_max_token(const int32_t* d_queries, int64_t n, int32_t* d_out,
                             hipStream_t stream);
