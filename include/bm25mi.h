@@ -650,6 +650,85 @@ int bm25_search_boolean_facets(bm25_index* idx, const int32_t* queries, int64_t 
                                float* out_scores, int64_t* out_total_hits, int64_t* out_facets);
 
 /*
+ * Numeric range filters: allow-masks made on the device from per-document
+ * numeric fields (a date range, a price range, a tenant id), the one common
+ * filter that otherwise has to be compared and packed on the host.  Replaces
+ * no reference call.
+ *
+ *   values  [F, n_docs]  one dtype per call, rows contiguous: values[f][d] = field f of
+ *                        handle-local document d.  kind: BM25_FIELD_I32 (0) int32,
+ *                        BM25_FIELD_F32 (1) float32, BM25_FIELD_I64 (2) int64.
+ *   fields  [M, C] int32 clause c of mask row m tests field fields[m][c]; negative = padding
+ *   lo, hi  [M, C]       of the values' dtype: the clause's bounds, both inclusive
+ *   base    [Mb, W]      Mb = 0 (NULL), 1 or M — exactly bm25_term_masks' base
+ *   out     [M, W] uint32, W = ceil(n_docs / 32), the layout of bm25_search_filtered
+ *
+ *   allowed(m, d) = d < n_docs and base(m, d)
+ *                   and for every c with fields[m][c] >= 0:
+ *                       lo[m][c] <= values[fields[m][c]][d] <= hi[m][c]
+ *
+ *   Comparisons are the dtype's own: int64 is compared as int64, never through
+ *   a float.  float32 is compared as IEEE: a NaN value fails every clause, and
+ *   -0.0f equals +0.0f.  Bounds may be +-inf or the integer limits: these are
+ *   the open ends.  lo > hi is an empty clause, and the row is all zeros.  A
+ *   row with no clause gives base, or every document when there is no base.
+ *   Clauses of one row are ANDed; several clauses may name the same field.
+ *   The mask guarantees of bm25_term_masks hold: Every word of every row is
+ *   written.  Bits at or past n_docs of the last word are written 0 even where
+ *   base has them set.  No word at index >= W of a row is read or written.  No
+ *   values entry at index >= n_docs of a field row is read.  M may pass 65535.
+ *   There are no global atomics and no scratch; the result does not depend on
+ *   scheduling.  base and out must not overlap.
+ *   Doc shards: values and bits are by the handle's own documents, so a shard
+ *   builds its slice of the collection's mask.
+ *   None of the three calls is a search on its own: bm25_range_masks and
+ *   bm25_range_masks_device leave bm25_search_dispatch, bm25_search_counters
+ *   and bm25_search_filtered_stats alone.
+ *   bm25_range_masks: host buffers, validated, synchronous.  BM25_EINVAL for a
+ *     NULL index, a bad kind, negative shapes, NULL pointers with non-empty
+ *     shapes, Mb not in {0, 1, M}, a fields entry >= F (the message names row,
+ *     column and value) and, float32 only, a NaN bound on a non-padding clause
+ *     (the message names it).  On any error the outputs are untouched.
+ *     M == 0 returns BM25_OK without device work.
+ *   bm25_range_masks_device: device buffers, enqueued on `stream`; checks
+ *     shapes and NULL pointers only, never synchronises, retains no scratch,
+ *     reads the caller's buffers only (no workspace, no index array) and is
+ *     not ordered against the handle's searches, as bm25_mask_facets_device is
+ *     not.  A field id >= F is a field that no document has: the clause
+ *     matches nothing and nothing out of bounds is read (the rule of an unknown
+ *     term in must, for the same reason).  A NaN bound matches nothing, which
+ *     is what the comparison gives anyway.
+ *   bm25_search_boolean_ranges: bm25_search_boolean_facets plus (values, kind,
+ *     F, fields, lo, hi, C) with the rows [Q, C]: row q is, bit for bit, the
+ *     row bm25_search_filtered returns under the mask range(q) AND term
+ *     clauses(q) AND base; totals and facets are taken of that same mask.  The
+ *     columns (validated as bm25_range_masks validates them) go up once per
+ *     call; each chunk's range masks are built on the device into a second
+ *     buffer of the call's own, which is the chunk's per-row base of the term
+ *     masks, so the masks still never move to the host.  With ranges present
+ *     the automatic chunk halves, so the two buffers together stay within
+ *     1 GiB; an explicit bool_chunk keeps its meaning, queries per chunk.  With
+ *     F == 0, C == 0 or NULL values the call is bm25_search_boolean_facets,
+ *     chunk size included, which is this call without them.
+ */
+enum { BM25_FIELD_I32 = 0, BM25_FIELD_F32 = 1, BM25_FIELD_I64 = 2 };
+int bm25_range_masks(bm25_index* idx, const void* values, int32_t kind, int64_t F,
+                     const int32_t* fields, const void* lo, const void* hi, int64_t C, int64_t M,
+                     const uint32_t* base, int64_t Mb, uint32_t* out_masks);
+int bm25_range_masks_device(bm25_index* idx, const void* d_values, int32_t kind, int64_t F,
+                            const int32_t* d_fields, const void* d_lo, const void* d_hi, int64_t C,
+                            int64_t M, const uint32_t* d_base, int64_t Mb, uint32_t* d_out_masks,
+                            void* stream);
+int bm25_search_boolean_ranges(bm25_index* idx, const int32_t* queries, int64_t Q, int64_t T,
+                               int32_t k, const int32_t* must, int64_t A, const int32_t* any,
+                               int64_t B, const int32_t* must_not, int64_t N,
+                               const int32_t* min_match, const uint32_t* base, int64_t Mb,
+                               const int32_t* groups, int64_t G, const void* values, int32_t kind,
+                               int64_t F, const int32_t* fields, const void* lo, const void* hi,
+                               int64_t C, int32_t* out_docs, float* out_scores,
+                               int64_t* out_total_hits, int64_t* out_facets);
+
+/*
  * bm25.BM25's float64 path (the dense model's API keeps the reference's
  * precision).  bm25_index_set_values_f64 keeps a float64 copy of the index's
  * values beside it (the same CSC order; bm25_build_scores method 1 returns

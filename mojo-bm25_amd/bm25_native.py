@@ -237,7 +237,8 @@ class BM25v:
         return self._gpu.search_after(queries, top_k, after, weights, allow, qm)
 
     def search_boolean(self, queries, top_k: int, must=None, any=None, must_not=None,
-                       base=None, *, min_match=None, total_hits: bool = False, facets=None):
+                       base=None, *, min_match=None, total_hits: bool = False, facets=None,
+                       ranges=None):
         """search under boolean term filters (not in the reference, whose
         search has no term filter): query q ranks only the documents that hold
         every term of ``must[q]``, at least one of ``any[q]`` (when it names
@@ -253,9 +254,18 @@ class BM25v:
         masks are built and counted on the GPU.  ``facets=(groups, n_groups)``
         (groups: an integer group id per document, negative = none, as
         bm25mi.facet_codes makes them of labels) appends, as the last element,
-        the int64 [Q, n_groups] count of those documents per group."""
+        the int64 [Q, n_groups] count of those documents per group.
+        ``ranges=(values, fields, lo, hi)`` (or ``(values, lo, hi)`` for one
+        field; GpuIndex.range_masks describes them, bm25mi.range_rows makes the
+        last three of dicts) also asks, per query, for numeric fields of the
+        documents within inclusive bounds: a date or price range, tested on
+        the GPU."""
         if facets is not None and (not isinstance(facets, (tuple, list)) or len(facets) != 2):
             raise ValueError("facets must be a pair (groups, n_groups)")
+        if ranges is not None and (not isinstance(ranges, (tuple, list))
+                                   or len(ranges) not in (3, 4)):
+            raise ValueError("ranges must be a quadruple (values, fields, lo, hi) or, for one "
+                             "field, a triple (values, lo, hi)")
         if len(queries) == 0:
             empty = np.zeros((0, 0), dtype=self.dtype), np.zeros((0, 0), dtype=self.dtype)
             if total_hits:
@@ -293,11 +303,13 @@ class BM25v:
                 "of tokens in the index.")
         if self._gpu is None:
             raise ValueError("BM25v index not built. Call index() first.")
-        if facets is None:
-            return self._gpu.search_boolean(queries, top_k, clauses[0], clauses[1], clauses[2],
-                                            base, min_match=min_match, total_hits=total_hits)
+        more = {}  # (only what the caller gave: the call without them is the earlier one)
+        if facets is not None:
+            more["facets"] = facets
+        if ranges is not None:
+            more["ranges"] = ranges
         return self._gpu.search_boolean(queries, top_k, clauses[0], clauses[1], clauses[2], base,
-                                        min_match=min_match, total_hits=total_hits, facets=facets)
+                                        min_match=min_match, total_hits=total_hits, **more)
 
     def _compute_relevance_from_scores(self, queries, top_k: int, dtype=np.float32):
         """bm25_native.py:129-158 on the GPU: per query, negative ids dropped,

@@ -91,6 +91,12 @@ _SIGS = {
     "bm25_mask_facets_device": ([_P, _P, _I64, _P, _I64, _P, _P], ctypes.c_int),
     "bm25_search_boolean_facets": ([_P, _P, _I64, _I64, _I32, _P, _I64, _P, _I64, _P, _I64, _P,
                                     _P, _I64, _P, _I64, _P, _P, _P, _P], ctypes.c_int),
+    "bm25_range_masks": ([_P, _P, _I32, _I64, _P, _P, _P, _I64, _I64, _P, _I64, _P], ctypes.c_int),
+    "bm25_range_masks_device": ([_P, _P, _I32, _I64, _P, _P, _P, _I64, _I64, _P, _I64, _P, _P],
+                                ctypes.c_int),
+    "bm25_search_boolean_ranges": ([_P, _P, _I64, _I64, _I32, _P, _I64, _P, _I64, _P, _I64, _P,
+                                    _P, _I64, _P, _I64, _P, _I32, _I64, _P, _P, _P, _I64, _P, _P,
+                                    _P, _P], ctypes.c_int),
     "bm25_index_set_values_f64": ([_P, _P], ctypes.c_int),
     "bm25_scores_dense_f64": ([_P, _P, _I64, _P], ctypes.c_int),
     "bm25_topn_f64": ([_P, _P, _I64, _I64, _P, _P], ctypes.c_int),

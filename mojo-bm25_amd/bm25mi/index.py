@@ -136,6 +136,113 @@ def _facet_groups(groups, n_groups, n_docs: int):
     return np.ascontiguousarray(g, dtype=np.int32), G
 
 
+# BM25_FIELD_I32 / _F32 / _I64: the dtypes a range filter's columns may have
+_FIELD_KINDS = {np.dtype(np.int32): 0, np.dtype(np.float32): 1, np.dtype(np.int64): 2}
+
+
+def _field_limits(dtype):
+    """(lowest, highest) bound of a column dtype: the open ends of a range."""
+    dt = np.dtype(dtype)
+    if dt not in _FIELD_KINDS:
+        raise ValueError(f"dtype {dt} is not a range filter's: int32, int64 or float32")
+    if dt.kind == "f":
+        return dt.type(-np.inf), dt.type(np.inf)
+    return dt.type(np.iinfo(dt).min), dt.type(np.iinfo(dt).max)
+
+
+def range_rows(rows, columns, dtype):
+    """Per-row range dicts -> (fields int32 [M, C], lo, hi [M, C] of ``dtype``),
+    the clause rows of the range filters.  ``rows``: one dict per mask row,
+    column name -> (lo, hi), both inclusive, None = the open end (the dtype's
+    limit, or -inf / +inf), e.g. [{"year": (2019, 2021), "price": (None, 50)},
+    {}]; ``columns``: the names of the values' rows, in order.  Rows are
+    padded to a common width with field -1 (bounds 0).  An unknown column
+    name is a ValueError, as is a bound the dtype cannot hold exactly."""
+    dt = np.dtype(dtype)
+    low, high = _field_limits(dt)
+    names = {name: i for i, name in enumerate(columns)}
+    rows = list(rows)
+    C = max((len(r) for r in rows), default=0)
+    fields = np.full((len(rows), C), -1, np.int32)
+    lo = np.zeros((len(rows), C), dt)
+    hi = np.zeros((len(rows), C), dt)
+    for m, r in enumerate(rows):
+        for c, (name, bounds) in enumerate(r.items()):
+            if name not in names:
+                raise ValueError(f"row {m}: unknown column {name!r} (columns: {list(columns)})")
+            if not isinstance(bounds, (tuple, list)) or len(bounds) != 2:
+                raise ValueError(f"row {m}, column {name!r}: the bounds are a pair (lo, hi)")
+            fields[m, c] = names[name]
+            for arr, b, end in ((lo, bounds[0], low), (hi, bounds[1], high)):
+                if b is None:
+                    arr[m, c] = end
+                    continue
+                if dt.kind == "i" and (int(b) != b or not int(low) <= int(b) <= int(high)):
+                    raise ValueError(f"row {m}, column {name!r}: bound {b!r} is no {dt}")
+                arr[m, c] = int(b) if dt.kind == "i" else b
+    return fields, lo, hi
+
+
+def _range_args(values, fields, lo, hi, n_docs: int, rows=None, what: str = "mask"):
+    """The (values, fields, lo, hi) of the range calls -> (values [F, n_docs],
+    kind, fields int32 [M, C], lo, hi [M, C] of the values' dtype); shape and
+    dtype errors are raised here, before any C call."""
+    v = np.asarray(values)
+    if v.dtype not in _FIELD_KINDS:
+        raise ValueError(f"values have dtype {v.dtype}: a range filter takes int32, int64 or "
+                         "float32 exactly (nothing is rounded or converted silently)")
+    if v.ndim == 1:
+        v = v[None, :]
+    if v.ndim != 2 or v.shape[1] != n_docs:
+        raise ValueError(f"values has shape {np.shape(values)}, expected ({n_docs},) or "
+                         f"(F, {n_docs}) (one entry per document)")
+    F = v.shape[0]
+    bounds = []
+    for name, b in (("lo", lo), ("hi", hi)):
+        a = np.asarray(b)
+        if a.dtype != v.dtype:
+            raise ValueError(f"{name} has dtype {a.dtype}, the values have {v.dtype} (bounds are "
+                             "of the values' dtype; bm25mi.range_rows makes them)")
+        if a.ndim == 1:
+            a = a[:, None]
+        if a.ndim != 2:
+            raise ValueError(f"{name} has shape {np.shape(b)}, expected (M,) or (M, C)")
+        bounds.append(np.ascontiguousarray(a))
+    lo_a, hi_a = bounds
+    if lo_a.shape != hi_a.shape:
+        raise ValueError(f"lo has shape {lo_a.shape}, hi has {hi_a.shape}")
+    M, C = lo_a.shape
+    if rows is not None and M != rows:
+        raise ValueError(f"lo and hi have {M} rows, expected {rows} (one per {what})")
+    if fields is None:
+        if F != 1:
+            raise ValueError(f"fields=None needs one field, the values have {F}")
+        f = np.zeros((M, C), np.int32)
+    else:
+        f = np.asarray(fields)
+        if f.dtype.kind not in "iu" or f.dtype == np.bool_:
+            raise ValueError("fields must be an integer array")
+        if f.ndim == 1:
+            f = f[:, None]
+        if f.shape != (M, C):
+            raise ValueError(f"fields has shape {np.shape(fields)}, lo and hi have {(M, C)}")
+        if f.size and int(f.max()) >= F:
+            m, c = np.argwhere(f >= F)[0]
+            raise ValueError(f"fields[{m}][{c}] = {int(f[m, c])} is not below F = {F}")
+        # (any negative id is padding: -1 fits int32 whatever the input's width)
+        f = np.ascontiguousarray(np.maximum(f.astype(np.int64), -1), dtype=np.int32)
+    return np.ascontiguousarray(v), _FIELD_KINDS[v.dtype], f, lo_a, hi_a
+
+
+def _ranges_arg(ranges):
+    """ranges= of search_boolean: (values, fields, lo, hi), or (values, lo, hi)
+    for one field -> the quadruple."""
+    if not isinstance(ranges, (tuple, list)) or len(ranges) not in (3, 4):
+        raise ValueError("ranges must be a quadruple (values, fields, lo, hi) or, for one field, "
+                         "a triple (values, lo, hi)")
+    return tuple(ranges) if len(ranges) == 4 else (ranges[0], None, ranges[1], ranges[2])
+
+
 AFTER_NONE = -2  # BM25_AFTER_NONE: an after-docs entry that means "no cursor"
 
 
@@ -913,8 +1020,85 @@ class GpuIndex:
             ctypes.c_void_p(d_groups.data_ptr()) if self.n_docs else None, G,
             ctypes.c_void_p(d_counts.data_ptr()) if M and G else None, ctypes.c_void_p(s)))
 
+    def range_masks(self, values, fields, lo, hi, base=None) -> np.ndarray:
+        """Allow-masks of numeric range filters (bm25_range_masks, host arrays)
+        -> packed uint32 [M, W], the masks search_filtered takes: row m allows
+        the documents of this handle that base allows and with
+        lo[m][c] <= values[fields[m][c]][d] <= hi[m][c] for every clause c whose
+        field id is not negative (padding).  values: [n_docs] or [F, n_docs],
+        int32, int64 or float32 exactly (anything else is a ValueError: nothing
+        is rounded); lo, hi: [M, C] (or [M]: one clause a row) of the values'
+        dtype, both inclusive, the dtype's limits or +-inf as open ends
+        (bm25mi.range_rows makes the three of dicts); fields: int [M, C], or
+        None with one field: field 0 for every clause; base as term_masks'."""
+        v, kind, f, lo_a, hi_a = _range_args(values, fields, lo, hi, self.n_docs)
+        M, C = f.shape
+        b, Mb = None, 0
+        if base is not None:
+            b = self._masks_arg(base)
+            Mb = b.shape[0]
+            if Mb not in (1, M):
+                raise ValueError(f"base has {Mb} rows, expected 1 or {M}")
+        out = np.zeros((M, (self.n_docs + 31) // 32), np.uint32)
+        check(lib.bm25_range_masks(self._h, _ptr(v) if v.size else None, kind, v.shape[0],
+                                   _ptr(f) if f.size else None, _ptr(lo_a) if f.size else None,
+                                   _ptr(hi_a) if f.size else None, C, M,
+                                   _ptr(b) if Mb and b.size else None, Mb,
+                                   _ptr(out) if out.size else None))
+        return out
+
+    def range_masks_device(self, d_values, d_fields, d_lo, d_hi, d_out, d_base=None,
+                           stream=None) -> None:
+        """Device-resident range_masks (bm25_range_masks_device): torch values
+        [n_docs] or [F, n_docs] (int32, int64 or float32), int32 fields and
+        bounds of the values' dtype [M, C], packed base masks [1 or M, W] (or
+        None) in, packed masks d_out [M, W] (32-bit words) out, enqueued on
+        ``stream`` with no host synchronisation and no validation of values: a
+        field id >= F is a field that no document has, a NaN bound matches
+        nothing.  Reads the caller's tensors only, so it may overlap a search
+        of the same handle.  d_base and d_out must not overlap."""
+        import torch
+        W = (self.n_docs + 31) // 32
+        kinds = {torch.int32: 0, torch.float32: 1, torch.int64: 2}
+        if d_values.dtype not in kinds:
+            raise ValueError(f"d_values has dtype {d_values.dtype}: int32, int64 or float32")
+        if (d_values.dim() not in (1, 2) or d_values.shape[-1] != self.n_docs
+                or not d_values.is_contiguous()):
+            raise ValueError(f"d_values must be a contiguous [{self.n_docs}] or "
+                             f"[F, {self.n_docs}] tensor (one entry per document)")
+        F = 1 if d_values.dim() == 1 else d_values.shape[0]
+        if (d_out.dim() != 2 or d_out.shape[1] != W or d_out.element_size() != 4
+                or not d_out.is_contiguous()):
+            raise ValueError(f"d_out must be a contiguous packed [M, {W}] tensor of 32-bit words")
+        M = d_out.shape[0]
+        if (d_fields.dim() != 2 or d_fields.shape[0] != M or d_fields.dtype != torch.int32
+                or not d_fields.is_contiguous()):
+            raise ValueError(f"d_fields must be a contiguous int32 [{M}, C] tensor (one row per "
+                             "mask)")
+        C = d_fields.shape[1]
+        for name, t in (("d_lo", d_lo), ("d_hi", d_hi)):
+            if (t.dtype != d_values.dtype or tuple(t.shape) != (M, C) or not t.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous {d_values.dtype} [{M}, {C}] tensor "
+                                 "(the values' dtype, the shape of d_fields)")
+        Mb = 0
+        if d_base is not None:
+            if (d_base.dim() != 2 or d_base.shape[1] != W or d_base.element_size() != 4
+                    or not d_base.is_contiguous()):
+                raise ValueError(f"d_base must be a contiguous packed [1 or M, {W}] tensor of "
+                                 "32-bit words")
+            Mb = d_base.shape[0]
+            if Mb not in (1, M):
+                raise ValueError(f"d_base has {Mb} rows, expected 1 or {M}")
+        s = getattr(stream, "cuda_stream", stream) or 0
+        p = lambda t, n: ctypes.c_void_p(t.data_ptr()) if n else None
+        check(lib.bm25_range_masks_device(
+            self._h, p(d_values, F and self.n_docs), kinds[d_values.dtype], F, p(d_fields, M * C),
+            p(d_lo, M * C), p(d_hi, M * C), C, M, p(d_base, Mb and W), Mb, p(d_out, M and W),
+            ctypes.c_void_p(s)))
+
     def search_boolean(self, queries: np.ndarray, k: int, must=None, any=None, must_not=None,
-                       base=None, *, min_match=None, total_hits: bool = False, facets=None):
+                       base=None, *, min_match=None, total_hits: bool = False, facets=None,
+                       ranges=None):
         """Top-k of every query among the documents its clause row lets
         through (bm25_search_boolean, host arrays): search_filtered under
         term_masks(must, any, must_not, base) with one mask per query, the
@@ -925,7 +1109,11 @@ class GpuIndex:
         (bm25_search_boolean_min_match; k = 0 then gives the totals alone).
         facets=(groups, n_groups), as GpuIndex.facets takes them, appends the
         int64 [Q, n_groups] facet counts of each query's mask as the last
-        element of the tuple (bm25_search_boolean_facets)."""
+        element of the tuple (bm25_search_boolean_facets).
+        ranges=(values, fields, lo, hi), as GpuIndex.range_masks takes them
+        with one row per query (or (values, lo, hi) for one field), ANDs each
+        query's numeric range clauses into its mask, built on the device
+        (bm25_search_boolean_ranges); totals and facets are of that mask."""
         q = np.ascontiguousarray(queries, dtype=np.int32)
         if q.ndim != 2:
             raise ValueError("queries must be a 2-D [Q, T] int32 array")
@@ -936,9 +1124,30 @@ class GpuIndex:
             if not isinstance(facets, (tuple, list)) or len(facets) != 2:
                 raise ValueError("facets must be a pair (groups, n_groups)")
             fg, G = _facet_groups(facets[0], facets[1], self.n_docs)
+        if ranges is not None:
+            rv, kind, rf, rlo, rhi = _range_args(*_ranges_arg(ranges), self.n_docs, rows=Q,
+                                                 what="query")
         k = int(k)
         docs = np.zeros((Q, max(k, 0)), np.int32)
         scores = np.zeros((Q, max(k, 0)), np.float32)
+        if ranges is not None:
+            totals = np.zeros(Q, np.int64) if total_hits else None
+            counts = np.zeros((Q, G), np.int64) if facets is not None else None
+            give = bool(counts is not None and G and fg.size)
+            ranged = bool(rv.size and rf.size)  # (no clause, or no document: no range to test)
+            check(lib.bm25_search_boolean_ranges(
+                self._h, _ptr(q), Q, T, k, _ptr(mu), mu.shape[1], _ptr(an), an.shape[1], _ptr(mn),
+                mn.shape[1], _ptr(mm), _ptr(b) if Mb else None, Mb, _ptr(fg) if give else None,
+                G if give else 0, _ptr(rv) if ranged else None, kind, rv.shape[0] if ranged else 0,
+                _ptr(rf) if ranged else None, _ptr(rlo) if ranged else None,
+                _ptr(rhi) if ranged else None, rf.shape[1] if ranged else 0, _ptr(docs),
+                _ptr(scores), _ptr(totals), _ptr(counts) if give else None))
+            out = (docs, scores)
+            if total_hits:
+                out += (totals,)
+            if facets is not None:
+                out += (counts,)
+            return out
         if facets is not None:
             totals = np.zeros(Q, np.int64) if total_hits else None
             counts = np.zeros((Q, G), np.int64)

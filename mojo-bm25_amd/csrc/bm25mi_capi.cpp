@@ -1175,9 +1175,97 @@ int check_groups(const int32_t* groups, int64_t n_docs, int64_t G) {
   return BM25_OK;
 }
 
+// The range arguments' shapes and pointers (host and device calls alike).
+int check_range_shape(int32_t kind, int64_t F, const void* fields, const void* lo, const void* hi,
+                      int64_t C, int64_t M, const void* base, int64_t Mb) {
+  if (kind != BM25_FIELD_I32 && kind != BM25_FIELD_F32 && kind != BM25_FIELD_I64)
+    return fail(BM25_EINVAL, "kind = %d: BM25_FIELD_I32 (0), BM25_FIELD_F32 (1) or BM25_FIELD_I64 (2)",
+                (int)kind);
+  if (F < 0 || C < 0 || M < 0 || Mb < 0) return fail(BM25_EINVAL, "negative range or mask shape");
+  if (Mb != 0 && Mb != 1 && Mb != M)
+    return fail(BM25_EINVAL, "base masks: Mb = %lld must be 0, 1 or M = %lld", (long long)Mb,
+                (long long)M);
+  if (M == 0) return BM25_OK;
+  if (C > 0 && !fields) return fail(BM25_EINVAL, "NULL fields");
+  if (C > 0 && (!lo || !hi)) return fail(BM25_EINVAL, "NULL bounds");
+  if (Mb > 0 && !base) return fail(BM25_EINVAL, "NULL base");
+  return BM25_OK;
+}
+
+size_t field_bytes(int32_t kind) { return kind == BM25_FIELD_I64 ? 8 : 4; }
+
+// Host range clauses: a field id >= F names no field (a negative one is
+// padding), and a float32 NaN bound would silently match nothing.
+int check_ranges(int32_t kind, int64_t F, const int32_t* fields, const void* lo, const void* hi,
+                 int64_t C, int64_t M) {
+  const float* flo = kind == BM25_FIELD_F32 ? (const float*)lo : nullptr;
+  const float* fhi = kind == BM25_FIELD_F32 ? (const float*)hi : nullptr;
+  for (int64_t m = 0; m < M; ++m)
+    for (int64_t c = 0; c < C; ++c) {
+      const int64_t i = m * C + c;
+      if (fields[i] < 0) continue;
+      if (fields[i] >= F)
+        return fail(BM25_EINVAL, "fields[%lld][%lld] = %d is not below F = %lld", (long long)m,
+                    (long long)c, fields[i], (long long)F);
+      if (flo && (flo[i] != flo[i] || fhi[i] != fhi[i]))
+        return fail(BM25_EINVAL, "%s[%lld][%lld] is NaN", flo[i] != flo[i] ? "lo" : "hi",
+                    (long long)m, (long long)c);
+    }
+  return BM25_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int bm25_range_masks(bm25_index* h, const void* values, int32_t kind, int64_t F,
+                     const int32_t* fields, const void* lo, const void* hi, int64_t C, int64_t M,
+                     const uint32_t* base, int64_t Mb, uint32_t* out_masks) {
+  if (!h) return fail(BM25_EINVAL, "NULL index");
+  int rc = check_range_shape(kind, F, fields, lo, hi, C, M, base, Mb);
+  if (rc) return rc;
+  const int64_t n_docs = h->ix.n_docs, W = (n_docs + 31) >> 5;
+  if (M == 0 || W == 0) return BM25_OK;
+  if (!out_masks) return fail(BM25_EINVAL, "NULL output");
+  if (F > 0 && !values) return fail(BM25_EINVAL, "NULL values");
+  rc = check_ranges(kind, F, fields, lo, hi, C, M);
+  if (rc) return rc;
+  Enter in(h);
+  if (in.rc) return in.rc;
+  const int64_t es = (int64_t)field_bytes(kind);
+  HostCall c(h->stream);
+  const char* d_values = c.upload((const char*)values, F * n_docs * es);
+  const int32_t* d_fields = c.upload(fields, M * C);
+  const char* d_lo = c.upload((const char*)lo, M * C * es);
+  const char* d_hi = c.upload((const char*)hi, M * C * es);
+  const uint32_t* d_base = c.upload(base, Mb * W);
+  uint32_t* d_out = c.alloc<uint32_t>(M * W);
+  if (c.ok())
+    c.run(launch_range_masks(h->ix, d_values, kind, F, d_fields, d_lo, d_hi, C, M, d_base, Mb,
+                             d_out, h->stream));
+  c.download(out_masks, d_out, M * W);
+  return c.finish("range_masks");
+}
+
+int bm25_range_masks_device(bm25_index* h, const void* d_values, int32_t kind, int64_t F,
+                            const int32_t* d_fields, const void* d_lo, const void* d_hi, int64_t C,
+                            int64_t M, const uint32_t* d_base, int64_t Mb, uint32_t* d_out_masks,
+                            void* stream) {
+  if (!h) return fail(BM25_EINVAL, "NULL index");
+  const int rc = check_range_shape(kind, F, d_fields, d_lo, d_hi, C, M, d_base, Mb);
+  if (rc) return rc;
+  if (M == 0 || h->ix.n_docs == 0) return BM25_OK;
+  if (!d_out_masks) return fail(BM25_EINVAL, "NULL output");
+  if (F > 0 && !d_values) return fail(BM25_EINVAL, "NULL values");
+  // reads the caller's buffers only (as bm25_mask_facets_device: no workspace,
+  // no index array, no ordering against the handle's searches)
+  Enter in(h);
+  if (in.rc) return in.rc;
+  HIP_TRY(launch_range_masks(h->ix, d_values, kind, F, d_fields, d_lo, d_hi, C, M, d_base, Mb,
+                             d_out_masks, (hipStream_t)stream),
+          "range_masks launch");
+  return BM25_OK;
+}
 
 int bm25_term_masks(bm25_index* h, const int32_t* must, int64_t A, const int32_t* any, int64_t B,
                     const int32_t* must_not, int64_t N, int64_t M, const uint32_t* base, int64_t Mb,
@@ -1340,6 +1428,20 @@ int bm25_search_boolean_facets(bm25_index* h, const int32_t* queries, int64_t Q,
                                const int32_t* min_match, const uint32_t* base, int64_t Mb,
                                const int32_t* groups, int64_t G, int32_t* out_docs,
                                float* out_scores, int64_t* out_total_hits, int64_t* out_facets) {
+  return bm25_search_boolean_ranges(h, queries, Q, T, k, must, A, any, B, must_not, N, min_match,
+                                    base, Mb, groups, G, nullptr, BM25_FIELD_I32, 0, nullptr,
+                                    nullptr, nullptr, 0, out_docs, out_scores, out_total_hits,
+                                    out_facets);
+}
+
+int bm25_search_boolean_ranges(bm25_index* h, const int32_t* queries, int64_t Q, int64_t T,
+                               int32_t k, const int32_t* must, int64_t A, const int32_t* any,
+                               int64_t B, const int32_t* must_not, int64_t N,
+                               const int32_t* min_match, const uint32_t* base, int64_t Mb,
+                               const int32_t* groups, int64_t G, const void* values, int32_t kind,
+                               int64_t F, const int32_t* fields, const void* lo, const void* hi,
+                               int64_t C, int32_t* out_docs, float* out_scores,
+                               int64_t* out_total_hits, int64_t* out_facets) {
   if (!h) return fail(BM25_EINVAL, "NULL index");
   if (Q < 0 || T < 0) return fail(BM25_EINVAL, "negative query shape");
   int rc = check_clauses(must, A, any, B, must_not, N, Q, base, Mb);
@@ -1348,6 +1450,13 @@ int bm25_search_boolean_facets(bm25_index* h, const int32_t* queries, int64_t Q,
   if (rc) return rc;
   rc = check_facet_shape(Q, G);
   if (rc) return rc;
+  if (F < 0 || C < 0) return fail(BM25_EINVAL, "negative range or mask shape");
+  // (F == 0, C == 0 or no values: no range clause, today's path unchanged)
+  const bool ranged = values && F > 0 && C > 0;
+  if (ranged) {
+    rc = check_range_shape(kind, F, fields, lo, hi, C, Q, nullptr, 0);
+    if (rc) return rc;
+  }
   if (G > 0 && (groups == nullptr) != (out_facets == nullptr))
     return fail(BM25_EINVAL, "facets: groups and out_facets come together (one of them is NULL)");
   if (G == 0 || !groups) out_facets = nullptr;  // (no group: no facet row to write)
@@ -1365,6 +1474,10 @@ int bm25_search_boolean_facets(bm25_index* h, const int32_t* queries, int64_t Q,
     rc = check_groups(groups, h->ix.n_docs, G);
     if (rc) return rc;
   }
+  if (ranged) {
+    rc = check_ranges(kind, F, fields, lo, hi, C, Q);
+    if (rc) return rc;
+  }
   Enter in(h);
   if (in.rc) return in.rc;
   rc = ensure_io(h, k > 0 ? Q * T : 0, Q * (int64_t)k);
@@ -1377,8 +1490,10 @@ int bm25_search_boolean_facets(bm25_index* h, const int32_t* queries, int64_t Q,
     if (out_facets) std::fill(out_facets, out_facets + Q * G, (int64_t)0);
     return BM25_OK;
   }
-  int64_t chunk = h->ix.opt.bool_chunk > 0 ? h->ix.opt.bool_chunk
-                                           : std::max<int64_t>(1, ((int64_t)1 << 28) / W);
+  // (with ranges a chunk holds two buffers: the automatic chunk halves)
+  int64_t chunk = h->ix.opt.bool_chunk > 0
+                      ? h->ix.opt.bool_chunk
+                      : std::max<int64_t>(1, ((int64_t)1 << (ranged ? 27 : 28)) / W);
   chunk = std::min(chunk, Q);
   std::vector<int32_t> ids((size_t)chunk);
   for (int64_t i = 0; i < chunk; ++i) ids[(size_t)i] = (int32_t)i;
@@ -1393,16 +1508,32 @@ int bm25_search_boolean_facets(bm25_index* h, const int32_t* queries, int64_t Q,
   const int32_t* d_groups = out_facets ? c.upload(groups, h->ix.n_docs) : nullptr;
   int64_t* d_facets = out_facets ? c.alloc<int64_t>(Q * G) : nullptr;
   uint32_t* d_masks = c.alloc<uint32_t>(chunk * W);
+  // the columns go up once per call; every chunk's range masks land in a second
+  // buffer, the chunk's per-row base of the term masks (whose base and out are
+  // __restrict__: never one buffer)
+  const int64_t es = (int64_t)field_bytes(kind);
+  const char* d_values = ranged ? c.upload((const char*)values, F * h->ix.n_docs * es) : nullptr;
+  const int32_t* d_fields = ranged ? c.upload(fields, Q * C) : nullptr;
+  const char* d_lo = ranged ? c.upload((const char*)lo, Q * C * es) : nullptr;
+  const char* d_hi = ranged ? c.upload((const char*)hi, Q * C * es) : nullptr;
+  uint32_t* d_rmasks = ranged ? c.alloc<uint32_t>(chunk * W) : nullptr;
   int32_t* d_qm = c.alloc<int32_t>(chunk);
   c.upload_to(d_qm, ids.data(), chunk);
   if (k > 0) c.upload_to(h->d_q, queries, Q * T);
   int64_t n_dense = 0;
   for (int64_t q0 = 0; c.ok() && q0 < Q; q0 += chunk) {
     const int64_t n = std::min(chunk, Q - q0);
+    const uint32_t* cbase = Mb == Q && Q > 1 ? d_base + q0 * W : d_base;
+    int64_t cMb = Mb == 0 ? 0 : (Mb == 1 ? 1 : n);
+    if (ranged) {
+      c.run(launch_range_masks(h->ix, d_values, kind, F, d_fields + q0 * C, d_lo + q0 * C * es,
+                               d_hi + q0 * C * es, C, n, cbase, cMb, d_rmasks, h->stream));
+      if (!c.ok()) break;
+      cbase = d_rmasks;
+      cMb = n;
+    }
     c.run(launch_term_masks(h->ix, d_must + q0 * A, A, d_any + q0 * B, B, d_not + q0 * N, N, n,
-                            Mb == Q && Q > 1 ? d_base + q0 * W : d_base,
-                            Mb == 0 ? 0 : (Mb == 1 ? 1 : n), d_masks, h->stream,
-                            d_mm ? d_mm + q0 : nullptr));
+                            cbase, cMb, d_masks, h->stream, d_mm ? d_mm + q0 : nullptr));
     // the chunk's counts, before its mask buffer is reused
     if (d_hits && c.ok()) c.run(launch_mask_count(h->ix, d_masks, n, d_hits + q0, h->stream));
     if (d_facets && c.ok())

@@ -567,6 +567,32 @@ hipError_t launch_mask_facets(const DevIndex& ix, const uint32_t* d_masks, int64
                               const int32_t* d_groups, int64_t G, int64_t* d_counts,
                               hipStream_t stream);
 
+// Numeric range filters (bm25mi_range.hip): d_out[M][W] in the layout above,
+// row m = the documents d < n_docs that d_base allows ([Mb][W], Mb = 0 (null:
+// every document), 1 or M, exactly launch_term_masks' base) and whose fields
+// pass every clause of the row: for every c with f = d_fields[m][c] >= 0,
+// d_lo[m][c] <= d_values[f][d] <= d_hi[m][c] in the values' own type (kind:
+// BM25_FIELD_I32 / _F32 / _I64; d_values [F][n_docs], d_lo and d_hi [M][C] of
+// that type).  A field id >= F is a field that no document has: the clause
+// matches nothing and no value is read.  Every word of every row is written
+// (bits at or past n_docs as 0, even where d_base has them set), no word at
+// index >= W of a row is read or written, no d_values entry at index >= n_docs
+// of a field row is read.  Reads the caller's buffers only; no atomics, no
+// scratch.  d_base and d_out must not overlap.  A workgroup takes a chunk of
+// kRangeChunkDocs documents and a block of up to kRangeRows rows; each of its
+// waves walks spans of kRangeSpanDocs documents in steps of 64.  Rows of up
+// to kRangeRegClauses clauses stay in the lanes' registers (kernels for 1, 2,
+// 4 and 8 of them); wider rows are read from memory per (step, row).
+enum { kFieldI32 = 0, kFieldF32 = 1, kFieldI64 = 2 };  // BM25_FIELD_* (include/bm25mi.h)
+constexpr int64_t kRangeRows = 64;          // mask rows of a row block (a lane per row)
+constexpr int64_t kRangeSpanDocs = 256;      // documents of a wave's span (8 words per lane)
+constexpr int64_t kRangeChunkDocs = 4096;    // documents of a workgroup's chunk (4 spans a wave)
+constexpr int64_t kRangeRegClauses = 8;      // clauses a row up to which a lane keeps them in registers
+hipError_t launch_range_masks(const DevIndex& ix, const void* d_values, int kind, int64_t F,
+                              const int32_t* d_fields, const void* d_lo, const void* d_hi,
+                              int64_t C, int64_t M, const uint32_t* d_base, int64_t Mb,
+                              uint32_t* d_out, hipStream_t stream);
+
 // Largest token id of [n] device ids (0 if none is positive) into *d_out.
 hipError_t launch_max_token(const int32_t* d_queries, int64_t n, int32_t* d_out,
                             hipStream_t stream);
