@@ -931,8 +931,11 @@ int bm25_search_stats_ex(bm25_index* idx, int64_t* rescored_tiles,
  *   path served the whole search; 0 after a search of k <= 4096),
  *   [6] non-empty term segments the REST pass dropped in tiles it scored
  *   (seg_skip: the term has no posting in a sub-block that can reach the
- *   threshold), [7] their postings — counted as [2] and [3], else -1.
- * n must be in 1..8. */
+ *   threshold), [7] their postings, [8] double rows (128 postings) the
+ *   REST pass dropped in the segments it kept (row_skip: all of the row's
+ *   postings lie in sub-blocks that cannot reach the threshold), [9] their
+ *   postings — counted as [2] and [3], else -1.
+ * n must be in 1..10. */
 int bm25_search_counters(bm25_index* idx, int64_t* out, int32_t n);
 
 /*
@@ -941,7 +944,8 @@ int bm25_search_counters(bm25_index* idx, int64_t* out, int32_t n);
  * BM25_LIST_CAP, BM25_CLAIM_CH, BM25_CLAIM_M, BM25_TILE_BOUND, BM25_THETA_BOUND,
  * BM25_GRID_PCT, BM25_LARGE_LISTS, BM25_COUNT_SKIPS, BM25_REST_SPLIT,
  * BM25_BOUND_POOL, BM25_FILTER_TILES, BM25_BOOL_CHUNK) and, for "tile_mask"
- * and "seg_skip", from BM25_TILE_MASK and BM25_SEG_SKIP, at bm25_index_create; these
+ * "seg_skip", "row_skip" and "row_mask_kb", from BM25_TILE_MASK, BM25_SEG_SKIP,
+ * BM25_ROW_SKIP and BM25_ROW_MASK_KB, at bm25_index_create; these
  * calls change or read them afterwards, effective from the next search.
  * Results never depend on them (every setting is bit-exact); they choose
  * kernels and geometry:
@@ -1008,6 +1012,15 @@ int bm25_search_counters(bm25_index* idx, int64_t* out, int32_t n);
  *                    sub-block whose masked bound reaches the threshold (the
  *                    pre-pass marks them: a byte per (query, tile)); needs
  *                    "tile_mask" and its table; 0: whole tiles only
+ *   "row_skip"       1 (default): of a kept segment of two or more double rows
+ *                    (128 postings each) the REST pass runs only the rows with
+ *                    a posting in such a sub-block (the pre-pass writes a u16
+ *                    per (query, tile, term lane) from the index's row masks);
+ *                    needs "seg_skip" and the row-mask table; 0: whole segments
+ *   "row_mask_kb"    budget of the row-mask table in KiB (default 262144), read
+ *                    at bm25_index_create only: terms with a segment of two or
+ *                    more rows take a slot of 64 B per tile, the most frequent
+ *                    first; a term past the budget keeps all its rows; 0: no table
  *   "grid_pct"      percent of the device's resident workgroup slots the
  *                    persistent score kernels launch (1..100, default 100):
  *                    below 100 leaves slots for kernels of another stream
@@ -1038,7 +1051,8 @@ int bm25_index_get_option(const bm25_index* idx, const char* name, int64_t* valu
  *                bm25_search_after(_device), whatever its cursors;
  *                32768: tile_skip_kernel, the tile bounds' pre-pass of a flat
  *                REST launch; 65536 (a flag): the pre-pass also marked the
- *                dead term segments of scored tiles (seg_skip)
+ *                dead term segments of scored tiles (seg_skip); 131072 (a
+ *                flag): ... and the dead rows of kept segments (row_skip)
  *   *term_lanes  flat kernel: term lanes per tile (8, 16, 32 or 64)
  *   band_tiles   [3]: flat kernel tiles per item of ALL, SAMPLE, REST
  *   *sample_p    sampling stride of the search (1: exact pass, 0: tile-bound

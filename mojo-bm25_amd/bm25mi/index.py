@@ -1252,6 +1252,8 @@ class GpuIndex:
                 "tile_skip": bool(km.value & 32768),
                 # ... and marked the dead term segments of scored tiles (bit 65536)
                 "seg_skip": bool(km.value & 65536),
+                # ... and the dead rows of the heavy terms' kept segments (bit 131072)
+                "row_skip": bool(km.value & 131072),
                 "term_lanes": tl.value,
                 "band_tiles": {"all": bt[0], "sample": bt[1], "rest": bt[2]},
                 "sample_p": sp_.value}
@@ -1262,13 +1264,15 @@ class GpuIndex:
         (query, tile) pairs the REST pass skipped by their tile bound and the
         postings of those pairs, queries left to the block merge, the
         non-empty term segments REST dropped in the tiles it scored and their
+        postings, the double rows it dropped in the segments it kept and their
         postings (counted like the skipped pairs: count_skips, else -1)."""
-        v = (ctypes.c_int64 * 8)()
-        check(lib.bm25_search_counters(self._h, v, 8))
+        v = (ctypes.c_int64 * 10)()
+        check(lib.bm25_search_counters(self._h, v, 10))
         return {"rescored_tiles": v[0], "fallback_queries": v[1],
                 "bound_skipped_tiles": v[2], "bound_skipped_postings": v[3],
                 "block_merge_queries": v[4], "large_dense_queries": v[5],
-                "bound_dropped_segments": v[6], "bound_dropped_postings": v[7]}
+                "bound_dropped_segments": v[6], "bound_dropped_postings": v[7],
+                "bound_dropped_rows": v[8], "bound_dropped_row_postings": v[9]}
 
 
 def merge_topk_device(device: int, d_docs, d_scores, W: int, Q: int, k: int, d_out_docs,

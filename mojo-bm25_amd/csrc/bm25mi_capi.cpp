@@ -235,9 +235,10 @@ int ensure_ws(bm25_index* h, int64_t Q, int64_t T, int k, hipStream_t st) {
   HIP_TRY(hipMalloc(&ws.sub_ipb, sizeof(int32_t)), "hipMalloc(sub_ipb)");
   HIP_TRY(hipMalloc(&ws.sub_done, sizeof(int32_t)), "hipMalloc(sub_done)");
   HIP_TRY(hipMemsetAsync(ws.sub_done, 0, sizeof(int32_t), st), "hipMemsetAsync(sub_done)");
-  // the REST pass's tile-skip bytes (tile_skip_kernel writes them per search)
+  // the REST pass's tile-skip words (tile_skip_kernel writes them per search)
   if (h->ix.bmax)
-    HIP_TRY(hipMalloc(&ws.tskip, (size_t)std::max<int64_t>(q * tskip_stride(nt), 4)), "hipMalloc(tskip)");
+    HIP_TRY(hipMalloc(&ws.tskip, sizeof(uint16_t) * 8 * (size_t)std::max<int64_t>(q * tskip_stride(nt), 1)),
+            "hipMalloc(tskip)");
   ws.cap_seg = need_seg;
   if (ws.cap_seg > 0) HIP_TRY(hipMalloc(&ws.seg, sizeof(uint64_t) * ws.cap_seg), "hipMalloc(seg)");
   ws.list_cap = C;
@@ -651,12 +652,60 @@ int bm25_index_create(int device, int64_t n_docs, int64_t n_terms, int64_t nnz,
     h->arrays = std::make_shared<IndexArrays>();
     h->arrays->device = device;
     h->arrays->p = {ix.indptr, ix.rel, ix.tl_ptr, ix.tl_tile, ix.tl_start, ix.ldoc, ix.val, ix.bmax,
-                    ix.bpool, ix.tmask};
+                    ix.bpool, ix.tmask, ix.hslot, ix.rowmask};
     *out = h;
   } else {
     bm25_index_destroy(h);
   }
   return rc;
+}
+
+// The row presence masks of the heavy terms (row_skip; DevIndex::rowmask),
+// beside tmask: the device marks the heavy terms, the host gives them table
+// slots in the order of their document frequency (largest first, the lower id
+// on a tie) while the budget lasts (row_mask_kb KiB; a slot is ntiles x 64 B),
+// the device fills the slots.  Optional like tmask: without the memory, or
+// without a heavy term, the handle stays without the table.
+static void build_row_masks(bm25_index* h, HostCall& c, const std::vector<int64_t>& ip) {
+  DevIndex& ix = h->ix;
+  const int64_t V = ix.n_terms;
+  const int64_t slot_bytes = (int64_t)sizeof(uint32_t) * kRowEntries * ix.ntiles;
+  const int64_t max_slots = ((int64_t)ix.opt.row_mask_kb << 10) / slot_bytes;
+  if (max_slots <= 0) return;
+  int32_t* d_heavy = c.alloc<int32_t>(V, "hipMalloc(heavy)");
+  std::vector<int32_t> heavy(V, 0);
+  if (c.ok()) c.run(launch_heavy_terms(ix, d_heavy, h->stream), "heavy_terms launch");
+  c.download(heavy.data(), d_heavy, V, "D2H heavy");
+  if (c.ok()) c.run(hipStreamSynchronize(h->stream), "heavy_terms");
+  if (!c.ok()) return;
+  std::vector<int32_t> hterm;
+  for (int64_t t = 0; t < V; ++t)
+    if (heavy[t]) hterm.push_back((int32_t)t);
+  std::stable_sort(hterm.begin(), hterm.end(), [&ip](int32_t x, int32_t y) {
+    return ip[x + 1] - ip[x] > ip[y + 1] - ip[y];
+  });
+  if ((int64_t)hterm.size() > max_slots) hterm.resize((size_t)max_slots);
+  if (hterm.empty()) return;
+  std::vector<int32_t> hslot(V, -1);
+  for (size_t i = 0; i < hterm.size(); ++i) hslot[hterm[i]] = (int32_t)i;
+  const int64_t H = (int64_t)hterm.size();
+  if (hipMalloc(&ix.hslot, sizeof(int32_t) * V) != hipSuccess ||
+      hipMalloc(&ix.rowmask, (size_t)(slot_bytes * H)) != hipSuccess) {
+    (void)hipGetLastError();
+    hipFree(ix.hslot);
+    ix.hslot = nullptr;
+    ix.rowmask = nullptr;
+    return;
+  }
+  ix.n_heavy = H;
+  int32_t* d_hterm = c.alloc<int32_t>(H, "hipMalloc(hterm)");
+  c.upload_to(ix.hslot, hslot.data(), V, "H2D hslot");
+  c.upload_to(d_hterm, hterm.data(), H, "H2D hterm");
+  if (c.ok()) c.run(launch_build_rowmask(ix, d_hterm, h->stream), "build_rowmask launch");
+  // the staged host vectors must outlive the copies, whatever failed since
+  const hipError_t es = hipStreamSynchronize(h->stream);
+  if (c.ok()) c.run(es, "build_rowmask");
+  if (c.ok()) h->device_bytes += (int64_t)sizeof(int32_t) * V + slot_bytes * H;
 }
 
 // The device layout of a new handle from the caller's CSC (ip: its indptr
@@ -754,6 +803,7 @@ static int build_index(bm25_index* h, const std::vector<int64_t>& ip, const int3
           hipMalloc(&ix.tmask, sizeof(uint32_t) * n_terms * bmax_stride(ntiles)) == hipSuccess) {
         c.run(launch_build_tmask(ix, h->stream), "build_tmask launch");
         h->device_bytes += (int64_t)(sizeof(uint32_t) * n_terms * bmax_stride(ntiles));
+        if (c.ok()) build_row_masks(h, c, ip);
       } else {
         (void)hipGetLastError();
         ix.tmask = nullptr;
@@ -802,7 +852,7 @@ int bm25_index_destroy(bm25_index* h) {
     for (void* x : {(void*)h->ix.indptr, (void*)h->ix.rel, (void*)h->ix.tl_ptr,
                     (void*)h->ix.tl_tile, (void*)h->ix.tl_start, (void*)h->ix.ldoc,
                     (void*)h->ix.val, (void*)h->ix.bmax, (void*)h->ix.bpool,
-                    (void*)h->ix.tmask})
+                    (void*)h->ix.tmask, (void*)h->ix.hslot, (void*)h->ix.rowmask})
       hipFree(x);
   }
   hipFree(h->ix.wbpool);  // (the handle's own pooled world bounds)
@@ -2123,7 +2173,7 @@ int bm25_search_stats_ex(bm25_index* h, int64_t* rescored_tiles, int64_t* fallba
 
 int bm25_search_counters(bm25_index* h, int64_t* out, int32_t n) {
   if (!h || !out) return fail(BM25_EINVAL, "NULL argument");
-  if (n < 1 || n > 8) return fail(BM25_EINVAL, "n=%d must be in 1..8", n);
+  if (n < 1 || n > 10) return fail(BM25_EINVAL, "n=%d must be in 1..10", n);
   Enter in(h);
   if (in.rc) return in.rc;
   int32_t cnt[kCounters] = {};
@@ -2134,9 +2184,12 @@ int bm25_search_counters(bm25_index* h, int64_t* out, int32_t n) {
   const bool counted = (h->ix.disp.kernels & kKCountSkips) != 0;
   uint64_t dpost = 0;
   std::memcpy(&dpost, cnt + 10, sizeof dpost);  // counters[10..11]: the dropped segments' postings
-  const int64_t v[8] = {cnt[3], cnt[2], counted ? cnt[5] : -1, counted ? (int64_t)post : -1,
-                        cnt[4], h->large_fallback, counted ? cnt[8] : -1,
-                        counted ? (int64_t)dpost : -1};
+  uint64_t rpost = 0;
+  std::memcpy(&rpost, cnt + 12, sizeof rpost);  // counters[12..13]: the dropped rows' postings
+  const int64_t v[10] = {cnt[3], cnt[2], counted ? cnt[5] : -1, counted ? (int64_t)post : -1,
+                         cnt[4], h->large_fallback, counted ? cnt[8] : -1,
+                         counted ? (int64_t)dpost : -1, counted ? cnt[9] : -1,
+                         counted ? (int64_t)rpost : -1};
   for (int i = 0; i < n; ++i) out[i] = v[i];
   return BM25_OK;
 }

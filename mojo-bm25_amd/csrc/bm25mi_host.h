@@ -138,6 +138,9 @@ inline constexpr OptDesc kOpts[] = {
 inline constexpr OptDesc kOptsMore[] = {
     {"tile_mask", "BM25_TILE_MASK", &SearchOpts::tile_mask, kOptBool, 0, 1, 0, nullptr},
     {"seg_skip", "BM25_SEG_SKIP", &SearchOpts::seg_skip, kOptBool, 0, 1, 0, nullptr},
+    {"row_skip", "BM25_ROW_SKIP", &SearchOpts::row_skip, kOptBool, 0, 1, 0, nullptr},
+    {"row_mask_kb", "BM25_ROW_MASK_KB", &SearchOpts::row_mask_kb, kOptRange, 0, 1 << 30, 2,
+     nullptr},
 };
 
 // Sets / reads one option by name (EINVAL names the accepted values).

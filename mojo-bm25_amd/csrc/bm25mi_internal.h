@@ -95,6 +95,10 @@ struct SearchOpts {
                            // read at index build too: 0 there keeps the handle without the table)
   int seg_skip = 1;        // REST drops the term segments of a scored tile that lie in dead
                            // sub-blocks only (the pre-pass's per-lane bits; needs tile_mask)
+  int row_skip = 1;        // ... and, of a heavy term's kept segment, the double rows whose
+                           // postings all lie in dead sub-blocks (needs seg_skip and rowmask)
+  int row_mask_kb = 262144;  // budget of the row-mask table in KiB, read at index build: the
+                           // lightest heavy terms past it get no slot and keep all their rows
 };
 
 // What the last search launched (bm25_search_dispatch).
@@ -113,6 +117,7 @@ enum {
   kKAfter = 16384,     // (a flag) the search came through bm25_search_after(_device)
   kKTileSkip = 32768,  // tile_skip_kernel: the tile bounds' pre-pass of a flat REST launch
   kKSegSkip = 65536,   // (a flag) ... and it marked the dead term segments of scored tiles
+  kKRowSkip = 131072,  // (a flag) ... and the dead rows of the heavy terms' kept segments
 };
 struct Dispatch {
   uint32_t kernels = 0;       // kK* bits of the score kernels launched
@@ -124,7 +129,7 @@ struct Dispatch {
 // Row stride of the tile-bound table: whole groups of four tiles (8 B).
 __host__ __device__ inline int64_t bmax_stride(int64_t ntiles) { return (ntiles + 3) & ~(int64_t)3; }
 
-// Row bytes of the REST pass's tile-skip table: a byte per tile, whole u32 words.
+// Row tiles of the REST pass's tile-skip table (eight u16 per tile), whole groups of four.
 __host__ __device__ inline int64_t tskip_stride(int64_t ntiles) { return (ntiles + 3) & ~(int64_t)3; }
 
 struct DevIndex {
@@ -160,6 +165,16 @@ struct DevIndex {
   // collects terms whose bit of its sub-block is set, which tightens the tile
   // bound (tile_skip_kernel); null: the whole-tile bound alone
   uint32_t* tmask = nullptr;
+  // Row presence masks of the heavy terms (row_skip; built where tmask is): a
+  // term is heavy when one of its segments has two or more of REST's double
+  // rows.  hslot[V]: the term's table slot h, -1 for a term that is not heavy
+  // or that the table's budget (row_mask_kb; slots go by document frequency)
+  // left out; rowmask[n_heavy][ntiles][kRowEntries]: bit s of entry r = row r
+  // of the term's segment in the tile has a posting in sub-block s (all ones
+  // in every entry of a segment of more than kRowEntries rows)
+  int32_t* hslot = nullptr;
+  uint32_t* rowmask = nullptr;
+  int64_t n_heavy = 0;
   // The same bounds pooled over groups of kPool consecutive tiles (the max of
   // each group's entries, [V][pstride], pstride = bmax_stride(ceil(ntiles /
   // kPool))): the threshold kernel's input where it holds enough groups — a
@@ -191,7 +206,8 @@ struct DevIndex {
   mutable Dispatch disp;  // written by the launchers (callers hold the handle's mutex)
 };
 
-constexpr int kCounters = 12;  // Workspace::counters
+constexpr int kCounters = 16;  // Workspace::counters
+constexpr int kRowEntries = 16;  // row masks of a (heavy term, tile)
 
 // A handle's reusable scratch for the large-k paths (bm25mi_large.hip): one
 // device allocation, bump-allocated by each search (nested uses stack), sized
@@ -266,7 +282,9 @@ struct Workspace {
                                  // [5] (query, tile) pairs REST skipped by their tile bound,
                                  // [6..7] (a u64) the postings of those pairs,
                                  // [8] term segments REST dropped in the tiles it scored,
-                                 // [10..11] (a u64) their postings ([9]: unused)
+                                 // [10..11] (a u64) their postings,
+                                 // [9] double rows REST dropped in the segments it kept,
+                                 // [12..13] (a u64) their postings
   int32_t* slow = nullptr;       // [Q] those queries
   // the large-k list path's REST (bm25mi_large.hip sets them on its copy):
   // per-(query, tile) slots of slot_cap keys and their counts; null otherwise
@@ -287,9 +305,10 @@ struct Workspace {
   uint32_t* sub = nullptr;
   int32_t* sub_ipb = nullptr;
   int32_t* sub_done = nullptr;
-  uint8_t* tskip = nullptr;      // [Q][tskip_stride(ntiles)]: a byte per (query, tile) — bit t
-                                 // set = REST drops term lane t's segment, 0xFF = it skips the
-                                 // tile (tile_skip_kernel writes every word of the searched
+  uint16_t* tskip = nullptr;     // [Q][tskip_stride(ntiles)][8]: a u16 per (query, tile, term
+                                 // lane) — 0 = REST drops the lane's segment (all eight: it
+                                 // skips the tile), 0xFFFF = every row runs, else bit r = row r
+                                 // runs (tile_skip_kernel writes every word of the searched
                                  // rows before each REST launch)
   uint64_t* seg = nullptr;       // sparse index: [Q][tiles/8][TT][8] segment of each (query,
                                  // term position, tile) (start | len << 32), built per search
@@ -343,6 +362,10 @@ hipError_t launch_build_tables(const DevIndex& ix, const int32_t* d_indices,
 hipError_t launch_build_bmax(const DevIndex& ix, hipStream_t stream);
 // Sub-block presence masks ix.tmask from the dense segment table and ldoc.
 hipError_t launch_build_tmask(const DevIndex& ix, hipStream_t stream);
+// Row presence masks (row_skip): heavy[t] = term t has a segment of two or
+// more double rows; then ix.rowmask for the ix.n_heavy terms d_hterm lists.
+hipError_t launch_heavy_terms(const DevIndex& ix, int32_t* d_heavy, hipStream_t stream);
+hipError_t launch_build_rowmask(const DevIndex& ix, const int32_t* d_hterm, hipStream_t stream);
 // out[r][g] = the max of in[r][kPool g .. kPool g + kPool - 1] (u16 f16 bits,
 // all >= 0) for rows r < rows, g < out_stride (zero past in_stride).
 hipError_t launch_pool_bounds(const uint16_t* in, int64_t rows, int64_t in_stride, uint16_t* out,

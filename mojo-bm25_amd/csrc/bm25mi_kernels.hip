@@ -55,9 +55,9 @@ struct IndexArgs {
   const uint32_t* tl_start;
   const uint64_t* seg;      // sparse + flat kernel: this search's segment table
   int64_t seg_zero;         // ... index of a zero entry past it
-  const uint8_t* tskip;     // flat REST with tile bounds: this search's skip bit of each
-                            // (query, tile) (tile_skip_kernel; null: no tile bounds)
-  int64_t tskip_stride;     // ... and its row bytes
+  const uint16_t* tskip;    // flat REST with tile bounds: this search's row word of each
+                            // (query, tile, term lane) (tile_skip_kernel; null: no tile bounds)
+  int64_t tskip_stride;     // ... and its row's tiles (8 words each)
 };
 
 static IndexArgs args_of(const DevIndex& ix) {
@@ -1051,8 +1051,8 @@ struct FlatCur {    // XCD-relative item ordinal, its claim's end, first phase t
 struct FlatDesc {   // lane tile * 2^TL + term: the term's segment in the tile (raw; r1 == r0: none)
   uint32_t ip, r0, r1;
   uint32_t aux;     // REST, one of (the launch never asks for both):
-                    //   tile bounds: the tile's skip bit (tile_skip_kernel; 0 outside
-                    //     the item)
+                    //   tile bounds: the lane's row word (tile_skip_kernel: 0 = dropped,
+                    //     0xFFFF = every row, else bit r = row r runs; 0 outside the item)
                     //   sample skip: score-key half of the tile's best sample key
 };
 
@@ -1091,7 +1091,21 @@ struct FlatCtx {    // the item the accumulator's tile belongs to
 // j0 - 1 (kNoTile at the item's first chunk: its first row starts a tile);
 // par = the item's context slot.
 constexpr uint32_t kNoTile = 0xFFFFFFFFu;
-template <int TL>
+// RW: sl carries the segment's row word in its high half (score_flat_kernel's
+// RW builds): 0xFFFF = every row runs, else row k of the chunk's numbering
+// is the segment's k-th row whose bit is set.
+__device__ __forceinline__ uint32_t kth_set_bit16(uint32_t m, uint32_t k) {
+  uint32_t pos = 0u;
+  uint32_t c = (uint32_t)__popc(m & 0xFFu);
+  if (k >= c) { k -= c; pos = 8u; m >>= 8; }
+  c = (uint32_t)__popc(m & 0xFu);
+  if (k >= c) { k -= c; pos += 4u; m >>= 4; }
+  c = (uint32_t)__popc(m & 3u);
+  if (k >= c) { k -= c; pos += 2u; m >>= 2; }
+  if (k >= (m & 1u)) pos += 1u;
+  return pos;
+}
+template <int TL, bool RW = false>
 __device__ __forceinline__ FlatTab flat_chunk(uint32_t sb, uint32_t sl, uint32_t incl,
                                               uint32_t excl, uint32_t total, uint32_t j0,
                                               uint32_t prev, uint32_t par) {
@@ -1105,10 +1119,14 @@ __device__ __forceinline__ FlatTab flat_chunk(uint32_t sb, uint32_t sl, uint32_t
   }
   const uint32_t e = (uint32_t)__shfl((int)excl, pos, 64);
   const uint32_t b = (uint32_t)__shfl((int)sb, pos, 64);
-  const uint32_t l = (uint32_t)__shfl((int)sl, pos, 64);
+  const uint32_t lw = (uint32_t)__shfl((int)sl, pos, 64);
+  const uint32_t l = RW ? (lw & 0xFFFFu) : lw;
   const bool in = j < total;
   FlatTab t;
-  const uint32_t k = j - e;  // row of its segment
+  uint32_t k = j - e;  // row of its segment
+  if constexpr (RW) {
+    if ((lw >> 16) != 0xFFFFu) k = kth_set_bit16(lw >> 16, k);
+  }
   t.base = (in && l != 0u) ? ((b & ~1u) + 128u * k) * 2u : 0u;
   // row positions p of the segment: p + base in [b, b + l)
   const uint32_t rlo = k == 0u ? (b & 1u) : 0u;
@@ -1133,7 +1151,7 @@ __host__ __device__ inline int flat_tl(int64_t T) {
   return T <= 8 ? 3 : (T <= 16 ? 4 : (T <= 32 ? 5 : 6));
 }
 
-template <int S, int PH, int SM, bool SP, int TL>
+template <int S, int PH, int SM, bool SP, int TL, bool RW = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BM25_FLAT_WPE, BM25_FLAT_WPE))) void score_flat_kernel(
     IndexArgs a, const int32_t* __restrict__ queries, int32_t T, int32_t P, int32_t G,
     int32_t nq_host, const int32_t* __restrict__ nq_dev, const int32_t* __restrict__ qmap,
@@ -1262,8 +1280,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BM25_FLAT_WP
   };
   // REST: sample tiles (groups of G = kSampleGroup tiles, one group per G * P)
   // whose best sample key is below theta are skipped
-  // (the tile bounds' skip bits: at 8 term lanes only, launch_flat)
-  constexpr bool kBits = PH == kRest && TL == 3 && SM != kLargeM;
+  // (the tile bounds' row words: the RW builds, which launch_flat takes exactly
+  // when it ran the pre-pass and set a.tskip — at 8 term lanes only; every other
+  // REST launch, the sample-skip one among them, runs a build without the words)
+  static_assert(!RW || (PH == kRest && TL == 3 && SM != kLargeM), "row words: 8-lane REST only");
+  constexpr bool kBits = RW;
   const bool skipping = PH == kRest && skeys != nullptr && G == kSampleGroup &&
                         !(kBits && a.tskip != nullptr);
   const uint32_t lgG = (uint32_t)__builtin_ctz((unsigned)G), lgP = (uint32_t)__builtin_ctz((unsigned)P);
@@ -1291,12 +1312,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BM25_FLAT_WP
       d.r1 = *(ok ? r + 1 : r);
     }
     d.aux = 0u;
-    if (kBits && a.tskip != nullptr) {  // this term lane's bit of the tile's byte, on every
-      // lane of the item's tiles: its segment is dropped (all eight: the tile is cut, and a
-      // padding or unknown term on the tile's first lane still counts it)
+    if (kBits && a.tskip != nullptr) {  // this term lane's row word of the tile, on every
+      // lane of the item's tiles: 0 = its segment is dropped (all eight: the tile is cut,
+      // and a padding or unknown term on the tile's first lane still counts it), 0xFFFF =
+      // every row runs, else bit r = row r of the segment runs (row_skip)
       const uint32_t t32 = (uint32_t)c.b + li;  // REST: phase tile = tile
       if ((int)li < c.bw)
-        d.aux = ((uint32_t)a.tskip[(int64_t)c.q * a.tskip_stride + t32] >> lt) & 1u;
+        d.aux = a.tskip[((int64_t)c.q * a.tskip_stride + t32) * 8 + lt];
     } else if (skipping) {  // the score-key half of this tile's best sample key
       // G and P are powers of two (sample_geom): shifts, no integer division
       const uint32_t t32 = (uint32_t)tile;
@@ -1318,6 +1340,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BM25_FLAT_WP
   uint32_t npost = 0;
   // ... and the non-empty segments this wave dropped in tiles that were scored, with their postings
   uint32_t ndrop = 0, ndpost = 0;
+  // ... and the rows its kept segments left out (row_skip), with their postings
+  uint32_t nrdrop = 0, nrpost = 0;
   // ---- the issue side's item: its segments (lane s = tile * TT + term) and
   // row numbering; the item prefetch pipeline one and two items ahead
   uint32_t iSb = 0, iSl = 0, iIncl = 0, iExcl = 0;
@@ -1343,13 +1367,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BM25_FLAT_WP
       // A scored tile's lane whose bit is set drops its segment alone: the
       // term has no posting in a sub-block that can reach theta.  Its tile
       // starts on the first remaining row, as with an absent term.
+      // A kept lane whose word is not 0xFFFF runs only the rows of its segment
+      // whose bit is set: the others hold postings of dead sub-blocks alone
+      // (row_skip; flat_chunk maps the k-th row that runs to its place).
       if (kBits && a.tskip != nullptr) {
-        const bool drop = dN.aux != 0u;
+        const bool drop = dN.aux == 0u;
         if constexpr (kCountPost) {
-          // the count_skips build: a cut tile sets all eight lanes; its postings
+          // the count_skips build: a cut tile clears all eight lanes; its postings
           // (lanes outside the item hold r1 == r0) are counted with the pair by
           // the tile's first term lane, a dropped segment's by its own lane
-          const bool cut = seg_sum_u32<TL>(dN.aux) == TT;
+          const bool cut = seg_sum_u32<TL>(drop ? 1u : 0u) == TT;
           const uint32_t sl = dN.r1 - dN.r0;
           const uint32_t tp = seg_sum_u32<TL>(sl);
           const bool cnt = cut && !skip && lt == 0u && (int)li < nx.bw;
@@ -1358,6 +1385,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BM25_FLAT_WP
           const bool dcnt = drop && !cut && !skip && sl != 0u;
           ndrop += (uint32_t)__popcll(__ballot(dcnt));
           ndpost += wave_sum_u32(dcnt ? sl : 0u);
+          // ... and the rows a kept segment leaves out, with their postings
+          const uint32_t b1 = (dN.ip + dN.r0) & 1u;
+          const uint32_t nf = sl == 0u ? 0u : (b1 + sl + 127u) >> 7;
+          const bool rcnt = !drop && !skip && dN.aux != 0xFFFFu;
+          uint32_t rr = 0u, rp = 0u;
+#pragma unroll
+          for (uint32_t r = 0; r < 16u; ++r) {
+            if (rcnt && r < nf && ((dN.aux >> r) & 1u) == 0u) {
+              ++rr;
+              rp += min(128u, b1 + sl - 128u * r) - (r == 0u ? b1 : 0u);
+            }
+          }
+          nrdrop += wave_sum_u32(rr);
+          nrpost += wave_sum_u32(rp);
         }
         skip = skip || drop;
       }
@@ -1365,6 +1406,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BM25_FLAT_WP
     iSb = dN.ip + dN.r0;
     iSl = skip ? 0u : dN.r1 - dN.r0;
     uint32_t nr = iSl == 0u ? 0u : ((iSb & 1u) + iSl + 127u) >> 7;
+    if constexpr (kBits) {
+      // (a segment is at most 2^S <= 4096 postings: its length and its row word share
+      // iSl, length in the low half; without tile bounds the word is 0xFFFF)
+      const uint32_t rw = a.tskip != nullptr ? dN.aux : 0xFFFFu;
+      if (rw != 0xFFFFu) nr = (uint32_t)__popc(rw & ~(0xFFFFFFFFu << min(nr, 16u)));
+      iSl |= rw << 16;
+    }
     // every tile of the item runs its epilogue (one row, possibly empty, in
     // each tile): ALL, and REST without a positive threshold
     if ((PH == kAll || (PH == kRest && !th_pos)) && lt == 0u && (int)li < nx.bw)
@@ -1444,12 +1492,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BM25_FLAT_WP
       il = 0;
       return;
     }
-    tI = flat_chunk<TL>(iSb, iSl, iIncl, iExcl, iTotal, iJ0, iPrev, iCur);
+    tI = flat_chunk<TL, kBits>(iSb, iSl, iIncl, iExcl, iTotal, iJ0, iPrev, iCur);
     nI = min(64u, iR - iJ0);
     il = 0;
   };
   enter_item();
-  tI = flat_chunk<TL>(iSb, iSl, iIncl, iExcl, iTotal, 0u, iPrev, iCur);
+  tI = flat_chunk<TL, kBits>(iSb, iSl, iIncl, iExcl, iTotal, 0u, iPrev, iCur);
   nI = min(64u, iR);
   il = 0;
 
@@ -1652,6 +1700,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BM25_FLAT_WP
     const uint32_t ndp = ndpost;
     if (lane == 0 && ndp != 0u)
       atomicAdd(reinterpret_cast<unsigned long long*>(stats + 5), (unsigned long long)ndp);
+    // stats + 4, + 7 .. + 8: the rows dropped in kept segments and (a u64) their postings
+    // (Workspace::counters[9], [12..13])
+    const uint32_t nrd = nrdrop;
+    if (lane == 0 && nrd != 0u) atomicAdd(stats + 4, (int32_t)nrd);
+    const uint32_t nrp = nrpost;
+    if (lane == 0 && nrp != 0u)
+      atomicAdd(reinterpret_cast<unsigned long long*>(stats + 7), (unsigned long long)nrp);
   }
   // every claim of this wave has returned (the last one, read by next(), ran
   // out of items) before it counts itself finished
@@ -1886,6 +1941,65 @@ __global__ __launch_bounds__(256) void build_tmask_kernel(const int64_t* __restr
   }
 }
 
+// Heavy terms (row_skip): heavy[t] = 1 when a segment of term t has two or
+// more of REST's double rows — for a segment [b, b + l) of absolute posting
+// indices, ((b & 1) + l + 127) >> 7 of them.
+__global__ __launch_bounds__(256) void heavy_terms_kernel(const int64_t* __restrict__ indptr,
+                                                          const uint32_t* __restrict__ rel,
+                                                          int64_t V, int64_t ntiles,
+                                                          int32_t* __restrict__ heavy) {
+  for (int64_t t = blockIdx.x; t < V; t += gridDim.x) {
+    const int64_t ip = indptr[t];
+    const uint32_t* r = rel + t * (ntiles + 1);
+    int any = 0;
+    for (int64_t j = threadIdx.x; j < ntiles; j += blockDim.x) {
+      const uint32_t l = r[j + 1] - r[j];
+      any |= (((uint32_t)(ip + r[j]) & 1u) + l + 127u) >> 7 >= 2u;
+    }
+    any = __syncthreads_or(any);
+    if (threadIdx.x == 0) heavy[t] = any;
+  }
+}
+
+// Row presence masks of the heavy terms that have a table slot (hterm[h] =
+// the term of slot h): rowmask[h][j][r] bit s = row r of the term's segment in
+// tile j has a posting in sub-block s, tmask's bit convention.  Row r of a
+// segment [b, b + l) holds the postings p with (b & ~1) + 128 r <= p < (b & ~1)
+// + 128 (r + 1): REST's rows (flat_chunk).  A segment of more than 16 rows
+// (an odd b under a full tile) keeps all ones: every row runs.
+__global__ __launch_bounds__(256) void build_rowmask_kernel(const int64_t* __restrict__ indptr,
+                                                            const uint32_t* __restrict__ rel,
+                                                            const uint16_t* __restrict__ ldoc,
+                                                            const int32_t* __restrict__ hterm,
+                                                            int64_t H, int64_t ntiles, int S,
+                                                            uint32_t* __restrict__ rowmask) {
+  for (int64_t h = blockIdx.x; h < H; h += gridDim.x) {
+    const int64_t t = hterm[h];
+    const int64_t ip = indptr[t];
+    const uint32_t* r = rel + t * (ntiles + 1);
+    for (int64_t j = threadIdx.x; j < ntiles; j += blockDim.x) {
+      uint32_t* out = rowmask + (h * ntiles + j) * kRowEntries;
+      const int64_t b = ip + r[j], e = ip + r[j + 1];
+      const int64_t b0 = b & ~(int64_t)1;
+      const bool wide = e > b && ((e - 1 - b0) >> 7) >= kRowEntries;
+      for (int i = 0; i < kRowEntries; ++i) out[i] = wide ? 0xFFFFFFFFu : 0u;
+      if (wide) continue;
+      int64_t cur = 0;
+      uint32_t m = 0u;
+      for (int64_t p = b; p < e; ++p) {
+        const int64_t row = (p - b0) >> 7;
+        if (row != cur) {
+          out[cur] = m;
+          m = 0u;
+          cur = row;
+        }
+        m |= 1u << ((uint32_t)ldoc[p] >> (S - 3));
+      }
+      if (e > b) out[cur] = m;
+    }
+  }
+}
+
 // The REST pass's tile bounds, ahead of it (theta is known): a block per
 // query and kSkipNT * N consecutive tiles (N below), so the table rows are read
 // coalesced along the tiles.  A tile is skipped
@@ -1907,16 +2021,23 @@ __global__ __launch_bounds__(256) void build_tmask_kernel(const int64_t* __restr
 // tile is cut iff L == 0).  With `seg`, term lane t of such a tile is dropped
 // iff (mk[t] & L) == 0 — the term has no posting in any live sub-block, so it
 // only adds to documents whose full sum stays below theta.
-// One byte per (query, tile): bit t = lane t's segment is dropped, 0xFF = the
-// tile is cut, 0 = everything is scored (always without a positive theta, and
-// past the last tile).  Every u32 word of the row is written.  tmask null:
-// the whole-tile bound alone (bytes 0 or 0xFF).
+// One u16 per (query, tile, term lane), eight per tile: 0 = lane t's segment is
+// dropped (all eight: the tile is cut), 0xFFFF = every row of it runs (always
+// without a positive theta, and past the last tile).  Every word of the row is
+// written.  tmask null: the whole-tile bound alone (words 0 or 0xFFFF).
+// With `rowmask` (row_skip; only with seg), a kept lane whose term is heavy
+// (hslot[term] = h >= 0) gets bit r = (rowmask[h][tile][r] & L) != 0 instead:
+// row r of its segment runs iff it has a posting in a live sub-block.  The
+// other rows hold postings of dead sub-blocks alone.  A segment
+// of more than 16 rows has all ones in its 16 entries (0xFFFF: every row), one
+// of r rows zeros from entry r on; (mk & L) != 0 gives a kept lane a row.
+// Whether a lane is heavy is the query's (uniform in the block): scalar branches.
 // A thread takes N = 1, 2 or 4 consecutive tiles: one wide load per table row
 // brings all of them (rows are whole groups of four tiles, bmax_stride), the
-// 2 x 8 loads of a thread are in flight together, and its bytes leave as one
-// store.  The tiles then run one after the other through the same registers,
-// so N is the most that still fills a block's threads (skip_npt): a short
-// row spreads over more threads instead.
+// 2 x 8 loads of a thread are in flight together, and each tile's words leave
+// as one 16-B store when the tile is done.  The tiles then run one after the other through the same
+// registers, so N is the most that still fills a block's threads (skip_npt):
+// a short row spreads over more threads instead.
 constexpr int kSkipNT = 256;
 constexpr int kSkipTerms = 8;  // the flat kernel's 8 term lanes (launch_flat)
 inline int skip_npt(int64_t ntiles) {
@@ -1927,12 +2048,13 @@ inline int skip_npt(int64_t ntiles) {
 constexpr uint32_t kSkipBias = 0x80000000u - 1048472u;
 template <int N> struct alignas(2 * N) SkipB { uint16_t v[N]; };
 template <int N> struct alignas(4 * N) SkipM { uint32_t v[N]; };
-template <int N> struct alignas(N) SkipO { uint8_t v[N]; };
+struct alignas(16) SkipW { uint16_t v[kSkipTerms]; };  // a tile's eight row words
 template <int N>
 __global__ __launch_bounds__(kSkipNT) void tile_skip_kernel(
     const uint16_t* __restrict__ bmax, const uint32_t* __restrict__ tmask, int64_t V,
     int64_t ntiles, const int32_t* __restrict__ queries, int32_t T, int64_t Q,
-    const uint64_t* __restrict__ theta, uint8_t* __restrict__ tskip, int32_t seg) {
+    const uint64_t* __restrict__ theta, uint16_t* __restrict__ tskip, int32_t seg,
+    const int32_t* __restrict__ hslot, const uint32_t* __restrict__ rowmask) {
   const int64_t bs = bmax_stride(ntiles);  // == tskip_stride(ntiles)
   const int64_t nch = (bs + kSkipNT * N - 1) / (kSkipNT * N);  // chunks that cover a row
   for (int64_t it = blockIdx.x; it < Q * nch; it += gridDim.x) {
@@ -1940,13 +2062,19 @@ __global__ __launch_bounds__(kSkipNT) void tile_skip_kernel(
     const int64_t t0 = ((it - q * nch) * kSkipNT + threadIdx.x) * N;  // the thread's first tile
     if (t0 >= bs) continue;  // (bs is a multiple of 4: the whole group lies in the row)
     const uint32_t thk = (uint32_t)(theta[q] >> 32);
-    SkipO<N> out;
+    SkipW* dst = reinterpret_cast<SkipW*>(tskip) + q * bs + t0;
+    SkipW all;
 #pragma unroll
-    for (int i = 0; i < N; ++i) out.v[i] = 0;
-    if (thk > score_key(0.f) && t0 < ntiles) {
+    for (int t = 0; t < kSkipTerms; ++t) all.v[t] = 0xFFFFu;
+    if (!(thk > score_key(0.f) && t0 < ntiles)) {
+#pragma unroll
+      for (int i = 0; i < N; ++i) dst[i] = all;
+    } else {
       SkipB<N> bb[kSkipTerms];
       SkipM<N> mm[kSkipTerms];
       uint32_t okm = 0u;  // (uniform) the term lanes with a known term
+      uint32_t hm = 0u;   // (uniform) ... and those of a heavy term: slot hs[t]
+      int32_t hs[kSkipTerms];
 #pragma unroll
       for (int t = 0; t < kSkipTerms; ++t) {
 #pragma unroll
@@ -1954,20 +2082,30 @@ __global__ __launch_bounds__(kSkipNT) void tile_skip_kernel(
           bb[t].v[i] = 0;
           mm[t].v[i] = 0u;
         }
+        hs[t] = -1;
         if (t < T) {
           const int32_t term = queries[q * T + t];
           if (term >= 0 && term < V) {
             okm |= 1u << t;
             bb[t] = *reinterpret_cast<const SkipB<N>*>(bmax + term * bs + t0);
             if (tmask != nullptr) mm[t] = *reinterpret_cast<const SkipM<N>*>(tmask + term * bs + t0);
+            if (seg && rowmask != nullptr) {
+              hs[t] = __builtin_amdgcn_readfirstlane(hslot[term]);
+              if (hs[t] >= 0) hm |= 1u << t;
+            }
           }
         }
       }
+      hm = (uint32_t)__builtin_amdgcn_readfirstlane((int)hm);
       const float th = key_score(thk);
       const float K = 1048576.f / th;
 #pragma unroll
       for (int i = 0; i < N; ++i) {
-        if (t0 + i >= ntiles) break;  // (bytes past the last tile stay 0)
+        if (t0 + i >= ntiles) {  // (words past the last tile: 0xFFFF)
+          dst[i] = all;
+          continue;
+        }
+        SkipW out;
         float ub[kSkipTerms];
         uint32_t mk[kSkipTerms];
 #pragma unroll
@@ -1977,13 +2115,13 @@ __global__ __launch_bounds__(kSkipNT) void tile_skip_kernel(
         }
         // (the order of the REST kernel's former segment sum over the 8 term lanes)
         const float sum = ((ub[0] + ub[1]) + (ub[2] + ub[3])) + ((ub[4] + ub[5]) + (ub[6] + ub[7]));
-        uint32_t byte = sum * 1.0001f < th ? 0xFFu : 0u;
+        uint32_t byte = sum * 1.0001f < th ? 0xFFu : 0u;  // bit t: lane t is dropped
+        uint32_t L = 0u;
         if (byte == 0u && tmask != nullptr) {
           uint32_t c[kSkipTerms];
 #pragma unroll
           for (int t = 0; t < kSkipTerms; ++t)
             c[t] = mk[t] != 0u ? (uint32_t)ceilf(fminf(ub[t] * K, 2097152.f)) + 1u : 0u;
-          uint32_t L = 0u;
 #pragma unroll
           for (int s = 31; s >= 0; --s) {
             uint32_t acc = kSkipBias;
@@ -1998,10 +2136,30 @@ __global__ __launch_bounds__(kSkipNT) void tile_skip_kernel(
             for (int t = 0; t < kSkipTerms; ++t) byte |= (mk[t] & L) == 0u ? 1u << t : 0u;
           }
         }
-        out.v[i] = (uint8_t)byte;
+#pragma unroll
+        for (int t = 0; t < kSkipTerms; ++t) out.v[t] = ((byte >> t) & 1u) ? 0u : 0xFFFFu;
+        if (hm != 0u && L != 0u) {  // (L != 0: the tile is scored, and seg holds)
+#pragma unroll
+          for (int t = 0; t < kSkipTerms; ++t) {
+            if (((hm >> t) & 1u) == 0u) continue;  // uniform
+            if ((byte >> t) & 1u) continue;
+            const uint4* rm = reinterpret_cast<const uint4*>(
+                rowmask + ((int64_t)hs[t] * ntiles + (t0 + i)) * kRowEntries);
+            uint32_t w = 0u;
+#pragma unroll
+            for (int g = 0; g < kRowEntries / 4; ++g) {
+              const uint4 m4 = rm[g];
+              w |= ((m4.x & L) != 0u ? 1u : 0u) << (4 * g);
+              w |= ((m4.y & L) != 0u ? 2u : 0u) << (4 * g);
+              w |= ((m4.z & L) != 0u ? 4u : 0u) << (4 * g);
+              w |= ((m4.w & L) != 0u ? 8u : 0u) << (4 * g);
+            }
+            out.v[t] = (uint16_t)w;
+          }
+        }
+        dst[i] = out;  // the tile's words: one 16-B store
       }
     }
-    *reinterpret_cast<SkipO<N>*>(tskip + q * bs + t0) = out;
   }
 }
 
@@ -3713,6 +3871,22 @@ hipError_t launch_build_tmask(const DevIndex& ix, hipStream_t stream) {
   return hipGetLastError();
 }
 
+hipError_t launch_heavy_terms(const DevIndex& ix, int32_t* d_heavy, hipStream_t stream) {
+  if (ix.n_terms == 0 || ix.ntiles == 0 || ix.sparse) return hipSuccess;
+  const int64_t blocks = std::min<int64_t>(ix.n_terms, 65536);
+  hipLaunchKernelGGL(heavy_terms_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, ix.indptr,
+                     ix.rel, ix.n_terms, ix.ntiles, d_heavy);
+  return hipGetLastError();
+}
+
+hipError_t launch_build_rowmask(const DevIndex& ix, const int32_t* d_hterm, hipStream_t stream) {
+  if (ix.n_heavy == 0 || ix.ntiles == 0 || !ix.rowmask || ix.sparse) return hipSuccess;
+  const int64_t blocks = std::min<int64_t>(ix.n_heavy, 65536);
+  hipLaunchKernelGGL(build_rowmask_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, ix.indptr,
+                     ix.rel, ix.ldoc, d_hterm, ix.n_heavy, ix.ntiles, ix.tile_shift, ix.rowmask);
+  return hipGetLastError();
+}
+
 hipError_t launch_count_tiles(const DevIndex& ix, const int32_t* d_indices, int64_t* d_cnt,
                               int32_t* d_err, hipStream_t stream) {
   if (ix.n_terms == 0) return hipSuccess;
@@ -3852,6 +4026,7 @@ static void launch_flat(const DevIndex& ix, const int32_t* q, int64_t T, int64_t
   // in groups of 8 tiles: ws.cand holds this shard's sample keys)
   const bool skip = PH == kRest && sg.sample_keys != nullptr && sg.M == 1 && sg.G == kSampleGroup;
   IndexArgs a = args_of(ix);
+  bool rw = false;  // the pre-pass ran: the REST build that reads its row words
   // one descriptor field: the sample keys' skip or the tile bounds; and the
   // bounds only at 8 term lanes (16 lanes: 4-tile items whose 16 bmax rows cost
   // more than the few tiles they skip — 5.45 vs 5.00 ms, 16-term queries).
@@ -3864,17 +4039,21 @@ static void launch_flat(const DevIndex& ix, const int32_t* q, int64_t T, int64_t
       ws.tskip != nullptr) {
     a.tskip = ws.tskip;
     a.tskip_stride = tskip_stride(ix.ntiles);
+    rw = true;
     const uint32_t* tmask = ix.opt.tile_mask ? ix.tmask : (const uint32_t*)nullptr;
     // the dead term segments of scored tiles: from the live mask, so with the masks only
     const bool seg = ix.opt.seg_skip && tmask != nullptr;
-    ix.disp.kernels |= kKTileSkip | (seg ? kKSegSkip : 0);
+    // ... and the dead rows of the heavy terms' kept segments: from the same mask
+    const bool row = seg && ix.opt.row_skip && ix.rowmask != nullptr && ix.hslot != nullptr;
+    ix.disp.kernels |= kKTileSkip | (seg ? kKSegSkip : 0) | (row ? kKRowSkip : 0);
     auto pre = [&](auto kern, int npt) {
       const int64_t per = (int64_t)kSkipNT * npt;
       const int64_t items = sg.nq_host * ((a.tskip_stride + per - 1) / per);
       const int grid = (int)std::min<int64_t>(items, persistent_grid(kern, kSkipNT));
       hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kSkipNT), 0, st, ix.bmax, tmask,
                          ix.n_terms, ix.ntiles, q, (int32_t)T, (int64_t)sg.nq_host, ws.theta,
-                         ws.tskip, (int32_t)seg);
+                         ws.tskip, (int32_t)seg, ix.hslot,
+                         row ? ix.rowmask : (const uint32_t*)nullptr);
     };
     switch (skip_npt(ix.ntiles)) {
       case 4: pre(tile_skip_kernel<4>, 4); break;
@@ -3910,6 +4089,9 @@ static void launch_flat(const DevIndex& ix, const int32_t* q, int64_t T, int64_t
                        PH == kRest ? ws.counters + 5 : nullptr, kSlots ? ws.slot_cnt : nullptr,
                        SM == kSplitM ? ws.sub : nullptr, SM == kSplitM ? ws.sub_ipb : nullptr);
   };
+  if constexpr (PH == kRest && TL == 3 && SM != kLargeM) {
+    if (rw) return go(score_flat_kernel<S, PH, SM, false, TL, true>);  // (bmax: a dense index)
+  }
   if (ix.sparse)
     go(score_flat_kernel<S, PH, SM, true, TL>);
   else
