@@ -448,6 +448,94 @@ int bm25_search_after_device(bm25_index* idx, const int32_t* d_queries, const fl
                              void* stream);
 
 /*
+ * Field collapsing (result diversification): at most per_group hits of every
+ * group in a row's top-k — "one hit per site", "at most two per author" —
+ * exact, on the device.  Over-fetching k x results and deduplicating on the
+ * host is wrong whenever one group holds more than k x of the best documents.
+ * Replaces no reference call: BM25v.search has no grouping
+ * (bm25_native.py:76-158).
+ *   queries, weights, masks, M, query_mask, out_docs / out_scores: exactly
+ *              bm25_search_after(_device): weights may be NULL (plain sums);
+ *              with M == 0 a NULL query_mask means no filter, with M >= 1 it
+ *              means mask 0; -1 = no filter for that row.
+ *   groups [n_docs] int32, by the handle's own documents: a value >= 0 is the
+ *              document's group, any non-negative int32 (there is no group
+ *              count and no table of groups: a hashed host name works; the
+ *              codes of bm25mi.facet_codes work too); a value < 0: the document
+ *              has no group.
+ *   per_group >= 1: the most hits of one group in a row.
+ * Row q: take the full result order of bm25_search_weighted under the row's
+ * mask (fp32 score descending, doc id ascending, zero-score allowed documents
+ * included) and walk it from rank 1 with a counter per group value:
+ *   a document with groups[d] < 0 is always kept;
+ *   a document with groups[d] = g >= 0 is kept iff fewer than per_group
+ *              documents of g were kept before it, and then g's counter goes up;
+ *   the row is the first k kept documents as (doc + doc_offset, score bits),
+ *              padded (doc -1 / score bits 0xFFFFFFFF) where fewer are kept.
+ * per_group >= k changes nothing: with it, with all groups negative or all
+ * distinct, every row is bit for bit bm25_search_weighted's (bm25_search's
+ * under NULL weights and no mask).  Returned scores are never -0.0f.
+ *   out_groups [Q, k] int32, optional (NULL: not wanted): groups[d] of each
+ *              hit, -1 in padding (a hit without a group reads as its own
+ *              negative value).  A doc-shard merge needs it.
+ *   0 <= k <= min(n_docs, 4096).  k > 4096 is BM25_EINVAL: collapse is limited
+ *              to 4096 because the per-row group table lives in LDS (8192 slots
+ *              of (group, count), 64 KiB).  k == 0 or Q == 0: BM25_OK, no
+ *              device work.
+ *   There is no cursor argument: paging collapsed results is out of scope (the
+ *              next page depends on the groups the earlier pages filled, which
+ *              a (score, doc) cursor does not carry).
+ * Doc shards: groups are by the handle's own documents and the ids come back
+ * global.  A document of the collection's collapsed top-k is inside its
+ * shard's collapsed top-k, so the shards' (doc, score, group) lists merged in
+ * key order and collapsed once more are exact; bm25mi.dist does
+ * not do this yet.
+ * How: rounds.  Round 1 is one cursor-search page of p results for every row
+ * (option "collapse_page"), walked in rank order against the row's group
+ * counters.  The rows that are neither full nor out of documents go on in
+ * compact sub-batches (option "collapse_chunk"): each round a page after the
+ * row's cursor under the row's mask minus every document of a saturated
+ * group, built on the device.  Such a round keeps at least one new hit, and
+ * where it leaves the row unfinished it saturated a new group: at most k + 1
+ * rounds a row; a filter that leaves one group ends in two.  Every round
+ * synchronises `stream` once, to read the number of unfinished rows (beside
+ * the filtered search's own possible synchronisation).
+ * Memory: the handle retains 8 p + 16 bytes per row of the largest batch
+ * (pages, cursors, counts, row ids; + 4 k where out_groups is NULL), like the
+ * large-k scratch; the rounds under exclusion masks take a buffer of the
+ * call's own, (8 T + 12 + 4 ceil(n_docs / 32)) bytes per sub-batch row, at
+ * most 1 GiB of mask words by default, released before the call returns.
+ *   bm25_search_collapsed: host buffers, validated, synchronous.  Validates as
+ *     bm25_search_after (token ids, finite weights, query_mask range, shapes,
+ *     NULLs); in addition NULL groups, per_group < 1 and k > 4096 are
+ *     BM25_EINVAL and the message names the value.  On an error the outputs
+ *     are untouched.
+ *   bm25_search_collapsed_device: device buffers, enqueued on `stream` (and
+ *     synchronising it as said above); checks shapes, NULLs, k > 4096 and
+ *     per_group < 1 only.
+ *   bm25_search_collapsed_stats: the first n (1..4) of, for the handle's last
+ *     collapsed search: [0] rounds (the most any row took), [1] rows
+ *     unfinished after round 1, [2] page entries dropped as over-quota (ahead
+ *     of their row's last hit), [3] rows served under exclusion masks, summed
+ *     over the rounds.  No device wait.
+ * Both are searches of the handle: mutex, workspace and stream ordering as
+ * bm25_search_after.  bm25_search_dispatch reports the flag 262144 after a
+ * search through either call, with 16384 / 4096 / 64 / 8192 as the last round
+ * set them; bm25_search_filtered_stats describes the last round.  Results
+ * never depend on "collapse_page" or "collapse_chunk".
+ */
+int bm25_search_collapsed(bm25_index* idx, const int32_t* queries, const float* weights,
+                          int64_t Q, int64_t T, int32_t k, const uint32_t* masks, int64_t M,
+                          const int32_t* query_mask, const int32_t* groups, int32_t per_group,
+                          int32_t* out_docs, float* out_scores, int32_t* out_groups);
+int bm25_search_collapsed_device(bm25_index* idx, const int32_t* d_queries,
+                                 const float* d_weights, int64_t Q, int64_t T, int32_t k,
+                                 const uint32_t* d_masks, int64_t M, const int32_t* d_query_mask,
+                                 const int32_t* d_groups, int32_t per_group, int32_t* d_docs,
+                                 float* d_scores, int32_t* d_groups_out, void* stream);
+int bm25_search_collapsed_stats(bm25_index* idx, int64_t* out, int32_t n);
+
+/*
  * Boolean term filters: the allow-masks of "+rust -java" — must contain all
  * of these terms, at least one of those, none of these — built on the device
  * from the index's own postings, in exactly the layout
@@ -944,8 +1032,9 @@ int bm25_search_counters(bm25_index* idx, int64_t* out, int32_t n);
  * BM25_LIST_CAP, BM25_CLAIM_CH, BM25_CLAIM_M, BM25_TILE_BOUND, BM25_THETA_BOUND,
  * BM25_GRID_PCT, BM25_LARGE_LISTS, BM25_COUNT_SKIPS, BM25_REST_SPLIT,
  * BM25_BOUND_POOL, BM25_FILTER_TILES, BM25_BOOL_CHUNK) and, for "tile_mask"
- * "seg_skip", "row_skip" and "row_mask_kb", from BM25_TILE_MASK, BM25_SEG_SKIP,
- * BM25_ROW_SKIP and BM25_ROW_MASK_KB, at bm25_index_create; these
+ * "seg_skip", "row_skip", "row_mask_kb", "collapse_page" and "collapse_chunk",
+ * from BM25_TILE_MASK, BM25_SEG_SKIP, BM25_ROW_SKIP, BM25_ROW_MASK_KB,
+ * BM25_COLLAPSE_PAGE and BM25_COLLAPSE_CHUNK, at bm25_index_create; these
  * calls change or read them afterwards, effective from the next search.
  * Results never depend on them (every setting is bit-exact); they choose
  * kernels and geometry:
@@ -1021,6 +1110,12 @@ int bm25_search_counters(bm25_index* idx, int64_t* out, int32_t n);
  *                    at bm25_index_create only: terms with a segment of two or
  *                    more rows take a slot of 64 B per tile, the most frequent
  *                    first; a term past the budget keeps all its rows; 0: no table
+ *   "collapse_page"  bm25_search_collapsed: results per page of a round, 0..4096
+ *                    (clamped to [1, min(n_docs, 4096)]); 0 (default) =
+ *                    automatic: 2 k
+ *   "collapse_chunk" bm25_search_collapsed: rows per sub-batch of the rounds
+ *                    under exclusion masks; 0 (default) = automatic: at most
+ *                    1 GiB of mask words per sub-batch, at least one row
  *   "grid_pct"      percent of the device's resident workgroup slots the
  *                    persistent score kernels launch (1..100, default 100):
  *                    below 100 leaves slots for kernels of another stream
@@ -1052,7 +1147,10 @@ int bm25_index_get_option(const bm25_index* idx, const char* name, int64_t* valu
  *                32768: tile_skip_kernel, the tile bounds' pre-pass of a flat
  *                REST launch; 65536 (a flag): the pre-pass also marked the
  *                dead term segments of scored tiles (seg_skip); 131072 (a
- *                flag): ... and the dead rows of kept segments (row_skip)
+ *                flag): ... and the dead rows of kept segments (row_skip);
+ *                262144 (a flag): the last search was called through
+ *                bm25_search_collapsed(_device); the other bits are its last
+ *                round's
  *   *term_lanes  flat kernel: term lanes per tile (8, 16, 32 or 64)
  *   band_tiles   [3]: flat kernel tiles per item of ALL, SAMPLE, REST
  *   *sample_p    sampling stride of the search (1: exact pass, 0: tile-bound

@@ -236,6 +236,49 @@ class BM25v:
             qm = (np.zeros(Q, np.int32) if allow.ndim == 1 else np.arange(Q, dtype=np.int32))
         return self._gpu.search_after(queries, top_k, after, weights, allow, qm)
 
+    def search_collapsed(self, queries, top_k: int, groups, per_group: int = 1,
+                         allow=None) -> Tuple[np.ndarray, np.ndarray]:
+        """search with at most ``per_group`` hits of every group (not in the
+        reference, whose search has no grouping): "one hit per site".
+        ``groups`` is an integer [n_docs] array, one group per document (the
+        codes of bm25mi.facet_codes; a value < 0: no group).  Each row is the
+        walk of search's full order that keeps a document while its group has
+        room; rows with fewer hits end in padding (doc -1).  ``allow`` as in
+        search_filtered.  top_k <= 4096.  Returns search's tuple: doc ids
+        (int32) and scores (f32), [Q, top_k]."""
+        if len(queries) == 0:
+            return np.zeros((0, 0), dtype=self.dtype), np.zeros((0, 0), dtype=self.dtype)
+        if (not isinstance(queries, np.ndarray) or queries.ndim != 2
+                or not isinstance(queries[0][0], TokId)):
+            raise ValueError("The queries must be a list of list of query token IDs.")
+        Q = queries.shape[0]
+        if allow is not None:
+            allow = np.asarray(allow)
+            if allow.ndim not in (1, 2) or (allow.ndim == 2 and allow.shape[0] != Q):
+                raise ValueError("allow must be a [n_docs] mask or a [Q, n_docs] array with one "
+                                 "row per query.")
+        groups = np.asarray(groups)
+        if groups.ndim != 1 or groups.dtype.kind not in "iu":
+            raise ValueError("groups must be a 1-D integer array with one group per document.")
+        if per_group < 1:
+            raise ValueError(f"per_group={per_group} must be >= 1")
+        if top_k < 0:
+            raise ValueError("negative dimensions are not allowed")
+        if top_k > 4096:
+            raise ValueError(f"top_k={top_k}: a collapsed search is limited to top_k <= 4096")
+        max_token_id = int(queries.max(initial=0))
+        n_terms = self._gpu.n_terms if self._gpu is not None else len(self.doc_toks.indptr) - 1
+        if max_token_id >= n_terms:
+            raise ValueError(
+                f"The maximum token ID in the query ({max_token_id}) is higher than the number "
+                "of tokens in the index.")
+        if self._gpu is None:
+            raise ValueError("BM25v index not built. Call index() first.")
+        qm = None
+        if allow is not None:
+            qm = (np.zeros(Q, np.int32) if allow.ndim == 1 else np.arange(Q, dtype=np.int32))
+        return self._gpu.search_collapsed(queries, top_k, groups, per_group, None, allow, qm)
+
     def search_boolean(self, queries, top_k: int, must=None, any=None, must_not=None,
                        base=None, *, min_match=None, total_hits: bool = False, facets=None,
                        ranges=None):

@@ -71,6 +71,11 @@ _SIGS = {
                           ctypes.c_int),
     "bm25_search_after_device": ([_P, _P, _P, _I64, _I64, _I32, _P, _I64, _P, _P, _P, _P, _P, _P],
                                  ctypes.c_int),
+    "bm25_search_collapsed": ([_P, _P, _P, _I64, _I64, _I32, _P, _I64, _P, _P, _I32, _P, _P, _P],
+                              ctypes.c_int),
+    "bm25_search_collapsed_device": ([_P, _P, _P, _I64, _I64, _I32, _P, _I64, _P, _P, _I32, _P, _P,
+                                      _P, _P], ctypes.c_int),
+    "bm25_search_collapsed_stats": ([_P, _PI64, _I32], ctypes.c_int),
     "bm25_score_docs_weighted": ([_P, _P, _P, _I64, _I64, _P, _I64, _P], ctypes.c_int),
     "bm25_score_docs_weighted_device": ([_P, _P, _P, _I64, _I64, _P, _I64, _P, _P],
                                         ctypes.c_int),

@@ -798,6 +798,114 @@ class GpuIndex:
             self._h, vp(d_queries), vp(d_weights), Q, T, k, vp(d_masks) if M else None, M,
             vp(d_query_mask), vp(a_s), vp(a_d), vp(d_docs), vp(d_scores), ctypes.c_void_p(s)))
 
+    # ------------------------------------------------------ field collapsing
+    COLLAPSE_MAX_K = 4096   # the per-row group table lives in LDS
+
+    @classmethod
+    def _collapse_args(cls, k, per_group) -> Tuple[int, int]:
+        k, per_group = int(k), int(per_group)
+        if k > cls.COLLAPSE_MAX_K:
+            raise ValueError(f"k={k}: a collapsed search is limited to k <= {cls.COLLAPSE_MAX_K} "
+                             "(the per-row group table lives in LDS)")
+        if per_group < 1:
+            raise ValueError(f"per_group={per_group} must be >= 1")
+        return k, per_group
+
+    def search_collapsed(self, queries: np.ndarray, k: int, groups, per_group: int = 1,
+                         weights=None, masks=None, query_mask=None, return_groups: bool = False):
+        """Top-k with at most ``per_group`` hits of every group
+        (bm25_search_collapsed, host arrays): ``groups`` int32 [n_docs] by
+        this handle's own documents — any value >= 0 is a group (the codes of
+        bm25mi.facet_codes, a hashed host name), a value < 0 means no group.
+        Row q is the walk of search_weighted's full order under its mask that
+        keeps a document while its group has room, the first k kept, padded
+        (doc -1, score bits ~0).  weights (None: plain sums), masks and
+        query_mask as in search_after.  k <= 4096.  Returns (docs, scores), and
+        the hits' groups (-1 in padding) as a third array with
+        ``return_groups``."""
+        q = np.ascontiguousarray(queries, dtype=np.int32)
+        if q.ndim != 2:
+            raise ValueError("queries must be a 2-D [Q, T] int32 array")
+        Q, T = q.shape
+        w = None if weights is None else self._weights_arg(q, weights)
+        m = None if masks is None else self._masks_arg(masks)
+        M = 0 if m is None else m.shape[0]
+        qm = None
+        if query_mask is not None:
+            qm = np.ascontiguousarray(query_mask, dtype=np.int32)
+            if qm.ndim != 1 or qm.size != Q:
+                raise ValueError(f"query_mask must hold one mask id per query ({Q}), "
+                                 f"got shape {qm.shape}")
+            if qm.size and (int(qm.min()) < -1 or int(qm.max()) >= M):
+                raise ValueError(f"query_mask entries must be in [-1, {M})")
+        g = np.asarray(groups)
+        if g.dtype.kind not in "iu" or g.ndim != 1 or g.size != self.n_docs:
+            raise ValueError(f"groups must be an integer array of {self.n_docs} (n_docs) entries, "
+                             f"got {g.dtype} of shape {g.shape}")
+        if g.size and (int(g.max()) > 2**31 - 1 or int(g.min()) < -2**31):
+            raise ValueError("groups must fit int32")
+        g = np.ascontiguousarray(g, dtype=np.int32)
+        k, per_group = self._collapse_args(k, per_group)
+        docs = np.zeros((Q, max(k, 0)), np.int32)
+        scores = np.zeros((Q, max(k, 0)), np.float32)
+        og = np.zeros((Q, max(k, 0)), np.int32) if return_groups else None
+        check(lib.bm25_search_collapsed(self._h, _ptr(q), _ptr(w), Q, T, k,
+                                        _ptr(m) if M else None, M, _ptr(qm), _ptr(g), per_group,
+                                        _ptr(docs), _ptr(scores), _ptr(og)))
+        return (docs, scores, og) if return_groups else (docs, scores)
+
+    def search_collapsed_device(self, d_queries, k: int, d_groups, per_group, d_weights, d_masks,
+                                d_query_mask, d_docs, d_scores, d_groups_out=None,
+                                stream=None) -> None:
+        """Device-resident search_collapsed (bm25_search_collapsed_device):
+        torch int32 [Q, T] queries, int32 [n_docs] groups, float32 [Q, T]
+        weights (or None), packed masks [M, W] (or None) and int32 [Q] mask ids
+        (or None) in; int32 / float32 [Q, k] docs and scores and, optionally,
+        int32 [Q, k] groups out, enqueued on ``stream``.  No validation of
+        token ids, weights or mask ids.  It synchronises ``stream`` once per
+        round (one round where no row's first 2 k results overfill a
+        group)."""
+        if d_queries.dim() != 2:
+            raise ValueError("d_queries must be a 2-D [Q, T] tensor")
+        Q, T = d_queries.shape
+        if d_weights is not None and (
+                tuple(d_weights.shape) != (Q, T) or not d_weights.dtype.is_floating_point
+                or d_weights.element_size() != 4):
+            raise ValueError(f"d_weights must be a float32 [{Q}, {T}] tensor")
+        W = (self.n_docs + 31) // 32
+        M = 0
+        if d_masks is not None:
+            if d_masks.dim() != 2 or d_masks.shape[1] != W or d_masks.element_size() != 4:
+                raise ValueError(f"d_masks must be a packed [M, {W}] tensor of 32-bit words")
+            M = d_masks.shape[0]
+        if d_query_mask is not None and d_query_mask.numel() != Q:
+            raise ValueError(f"d_query_mask must hold one mask id per query ({Q})")
+        if (d_groups.dim() != 1 or d_groups.numel() != self.n_docs or d_groups.element_size() != 4
+                or d_groups.dtype.is_floating_point or not d_groups.is_contiguous()):
+            raise ValueError(f"d_groups must be a contiguous int32 [{self.n_docs}] (n_docs) tensor")
+        k, per_group = self._collapse_args(k, per_group)
+        if d_docs.numel() != Q * k or d_scores.numel() != Q * k:
+            raise ValueError(f"d_docs and d_scores must hold {Q} x {k} results")
+        if d_groups_out is not None and (d_groups_out.numel() != Q * k
+                                         or d_groups_out.element_size() != 4):
+            raise ValueError(f"d_groups_out must hold {Q} x {k} int32 groups")
+        s = getattr(stream, "cuda_stream", stream) or 0
+        vp = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        check(lib.bm25_search_collapsed_device(
+            self._h, vp(d_queries), vp(d_weights), Q, T, k, vp(d_masks) if M else None, M,
+            vp(d_query_mask), vp(d_groups), per_group, vp(d_docs), vp(d_scores),
+            vp(d_groups_out), ctypes.c_void_p(s)))
+
+    def collapse_stats(self) -> dict:
+        """Counters of the last collapsed search (bm25_search_collapsed_stats):
+        rounds (the most any row took), rows unfinished after round 1, page
+        entries dropped as over-quota, rows served under exclusion masks
+        (summed over the rounds)."""
+        v = (ctypes.c_int64 * 4)()
+        check(lib.bm25_search_collapsed_stats(self._h, v, 4))
+        return {"rounds": int(v[0]), "unfinished_rows": int(v[1]),
+                "dropped_entries": int(v[2]), "excluded_rows": int(v[3])}
+
     def score_docs_weighted(self, queries, weights, docs) -> np.ndarray:
         """score_docs under weighted query terms (bm25_score_docs_weighted,
         host arrays): out[q, c] is bit for bit the score search_weighted
@@ -1247,6 +1355,9 @@ class GpuIndex:
         check(lib.bm25_search_dispatch(self._h, ctypes.byref(km), ctypes.byref(tl), bt,
                                        ctypes.byref(sp_)))
         return {"kernels": {n for b, n in self.KERNELS.items() if km.value & b},
+                # the search came through search_collapsed (bit 262144; the set is its
+                # last round's)
+                "collapsed": bool(km.value & 262144),
                 # tile_skip_kernel ran ahead of REST (bit 32768): reported beside the
                 # set, whose exact contents callers compare against the phases taken
                 "tile_skip": bool(km.value & 32768),

@@ -107,6 +107,11 @@ struct bm25_index {
                                // (-1: the dense path served the whole search)
   LargeArena arena;            // the large-k paths' scratch (grown to what they last asked for)
   int64_t filtered_dense = 0;  // queries of the last filtered search the dense path served
+  // the collapsed search's state of its rows (run_collapsed), kept for the next
+  // one like the large-k scratch, and the last one's bm25_search_collapsed_stats
+  char* cstate = nullptr;
+  size_t cstate_bytes = 0;
+  int64_t cstats[4] = {0, 0, 0, 0};
 };
 
 static const OptDesc* find_opt(const char* name) {
@@ -518,6 +523,145 @@ int run_filtered(bm25_index* h, const int32_t* d_queries, int64_t Q, int64_t T, 
   return BM25_OK;
 }
 
+// The automatic page of a collapsed search at k (option collapse_page = 0):
+// twice k — a row of small groups drops few of its first results, so one round
+// serves it, and a page costs the cursor search little more than k results do
+// (DESIGN.md §4 has the sweep).
+int collapse_auto_page(int k) { return (int)std::min<int64_t>(kMaxK, 2 * (int64_t)k); }
+
+// A device buffer of one call's own.
+struct OwnBuffer {
+  char* p = nullptr;
+  ~OwnBuffer() { hipFree(p); }
+};
+
+// The collapsed search's loop on stream st (kernels: bm25mi_collapse.hip);
+// caller holds h->mu and has set the device.  Round 1 pages the whole batch
+// (run_filtered as the cursor search, no cursor) and walks the pages into the
+// rows; the rows left unfinished go on in compact sub-batches, each round a
+// page after the row's cursor under the row's mask minus its saturated groups.
+// A round kept at least one new hit of every row it left unfinished (the first
+// entry of such a page is of an open group), so a row takes at most k + 1
+// rounds; a round that left a row unfinished dropped an entry of it, that is,
+// saturated a new group.  The host waits for the stream once per round, for
+// the number of unfinished rows (beside the filtered search's own wait for
+// its overflowed lists).  d_groups_out may be null: the rows' groups are then
+// kept in the state.
+int run_collapsed(bm25_index* h, const int32_t* d_queries, const float* d_weights, int64_t Q,
+                  int64_t T, int k, const uint32_t* d_masks, int64_t M, const int32_t* d_qm,
+                  const int32_t* d_groups, int per_group, int32_t* d_docs, float* d_scores,
+                  int32_t* d_groups_out, hipStream_t st) {
+  if (Q == 0 || k == 0) return BM25_OK;
+  const int64_t n_docs = h->ix.n_docs, W = (n_docs + 31) >> 5;
+  const SearchOpts& o = h->ix.opt;
+  const int p = (int)std::max<int64_t>(
+      1, std::min<int64_t>(o.collapse_page > 0 ? o.collapse_page : collapse_auto_page(k),
+                           std::min<int64_t>(n_docs, kMaxK)));
+  // the state of the rows: not the arena's, which run_filtered resets per call
+  size_t need = 0;
+  auto part = [&need](int64_t bytes) {
+    const size_t at = need;
+    need += ((size_t)bytes + 255) & ~(size_t)255;
+    return at;
+  };
+  const size_t o_pd = part(4 * Q * p), o_ps = part(4 * Q * p), o_cs = part(4 * Q),
+               o_cd = part(4 * Q), o_cnt = part(4 * Q), o_rows = part(4 * Q), o_ctr = part(16),
+               o_og = d_groups_out ? 0 : part(4 * Q * k);
+  if (need > h->cstate_bytes) {
+    if (h->ws_stream) HIP_TRY(hipStreamSynchronize(h->ws_stream), "hipStreamSynchronize");
+    hipFree(h->cstate);
+    h->cstate = nullptr;
+    h->cstate_bytes = 0;
+    HIP_TRY(hipMalloc((void**)&h->cstate, need), "hipMalloc(collapse state)");
+    h->cstate_bytes = need;
+  }
+  HIP_TRY(order_ws(h, st), "workspace order");
+  char* const b = h->cstate;
+  int32_t* pd = (int32_t*)(b + o_pd);
+  float* ps = (float*)(b + o_ps);
+  float* cur_s = (float*)(b + o_cs);
+  int32_t* cur_d = (int32_t*)(b + o_cd);
+  int32_t* cnt = (int32_t*)(b + o_cnt);
+  int32_t* rows = (int32_t*)(b + o_rows);
+  unsigned long long* ctr = (unsigned long long*)(b + o_ctr);
+  int32_t* og = d_groups_out ? d_groups_out : (int32_t*)(b + o_og);
+  HIP_TRY(hipMemsetAsync(cur_d, 0xFE, 4 * Q, st), "hipMemsetAsync");  // (< -1: no cursor yet)
+  HIP_TRY(hipMemsetAsync(cnt, 0, 4 * Q, st), "hipMemsetAsync");
+  HIP_TRY(hipMemsetAsync(ctr, 0, 16, st), "hipMemsetAsync");
+  unsigned long long got[2] = {0, 0};
+  auto walk = [&](const int32_t* row_map, int64_t R) -> int {
+    HIP_TRY(launch_collapse_page(pd, ps, p, row_map, R, d_groups, n_docs, h->ix.doc_offset,
+                                 per_group, k, cnt, d_docs, d_scores, og, cur_s, cur_d, ctr, st),
+            "collapse walk");
+    HIP_TRY(hipMemcpyAsync(got, ctr, sizeof got, hipMemcpyDeviceToHost, st), "D2H unfinished");
+    HIP_TRY(hipStreamSynchronize(st), "collapse round sync");
+    return BM25_OK;
+  };
+  int rc = run_filtered(h, d_queries, Q, T, p, d_masks, M, d_qm, pd, ps, st, d_weights, true);
+  if (rc) return rc;
+  rc = walk(nullptr, Q);
+  if (rc) return rc;
+  const int64_t U = (int64_t)got[0];
+  int64_t rounds = 1, served = 0;
+  if (U > 0) {
+    HIP_TRY(launch_collapse_compact(cur_d, Q, rows, st), "collapse compact");
+    // rows per sub-batch: their exclusion masks stay within 1 GiB (automatic)
+    int64_t chunk = o.collapse_chunk > 0 ? o.collapse_chunk
+                                         : std::max<int64_t>(1, ((int64_t)1 << 28) / W);
+    chunk = std::min(chunk, U);
+    OwnBuffer own;
+    size_t cn = 0;
+    auto cpart = [&cn](int64_t bytes) {
+      const size_t at = cn;
+      cn += ((size_t)bytes + 255) & ~(size_t)255;
+      return at;
+    };
+    const size_t c_q = cpart(4 * chunk * T), c_w = cpart(d_weights ? 4 * chunk * T : 0),
+                 c_as = cpart(4 * chunk), c_ad = cpart(4 * chunk), c_id = cpart(4 * chunk),
+                 c_ex = cpart(4 * chunk * W);
+    HIP_TRY(hipMalloc((void**)&own.p, std::max<size_t>(cn, 256)), "hipMalloc(collapse masks)");
+    int32_t* cq = (int32_t*)(own.p + c_q);
+    float* cw = d_weights ? (float*)(own.p + c_w) : nullptr;
+    float* as = (float*)(own.p + c_as);
+    int32_t* ad = (int32_t*)(own.p + c_ad);
+    int32_t* ids = (int32_t*)(own.p + c_id);
+    uint32_t* excl = (uint32_t*)(own.p + c_ex);
+    for (int64_t u0 = 0; u0 < U; u0 += chunk) {
+      const int64_t n = std::min(chunk, U - u0);
+      int64_t live = n, sub = 0;
+      while (live > 0) {
+        if (++sub > (int64_t)k + 1) {
+          hipStreamSynchronize(st);
+          return fail(BM25_EHIP, "collapsed search: a row took more than k + 1 = %d rounds", k + 1);
+        }
+        served += live;
+        HIP_TRY(launch_collapse_gather(rows + u0, n, d_queries, d_weights, T, cur_s, cur_d, cq, cw,
+                                       as, ad, ids, st),
+                "collapse gather");
+        HIP_TRY(launch_collapse_exclude(rows + u0, n, d_masks, M, d_qm, d_groups, n_docs,
+                                        per_group, k, cnt, og, cur_d, excl, st),
+                "collapse exclusion masks");
+        HIP_TRY(hipMemsetAsync(ctr, 0, 8, st), "hipMemsetAsync");
+        rc = run_filtered(h, cq, n, T, p, excl, n, ids, pd, ps, st, cw, true, as, ad);
+        if (rc) {
+          hipStreamSynchronize(st);
+          return rc;
+        }
+        rc = walk(rows + u0, n);
+        if (rc) return rc;
+        live = (int64_t)got[0];
+      }
+      rounds = std::max(rounds, 1 + sub);
+    }
+  }
+  h->ix.disp.kernels |= kKCollapsed;
+  h->cstats[0] = rounds;
+  h->cstats[1] = U;
+  h->cstats[2] = (int64_t)got[1];
+  h->cstats[3] = served;
+  return BM25_OK;
+}
+
 // Counters of the last search (caller holds h->mu); the search may run on a
 // caller's stream: wait for that stream, not for the device.
 void read_counters(bm25_index* h, int32_t (&cnt)[kCounters]) {
@@ -841,6 +985,7 @@ int bm25_index_destroy(bm25_index* h) {
     if (e) hipEventDestroy(e);
   free_ws(h->ws);
   hipFree(h->arena.base);
+  hipFree(h->cstate);
   hipFree(h->d_q);
   hipFree(h->d_docs);
   hipFree(h->d_scores);
@@ -1150,6 +1295,96 @@ int bm25_search_after_device(bm25_index* h, const int32_t* d_queries, const floa
   if (in.rc) return in.rc;
   return run_filtered(h, d_queries, Q, T, k, d_masks, M, d_query_mask, d_docs, d_scores,
                       (hipStream_t)stream, d_weights, true, d_after_scores, d_after_docs);
+}
+
+// The collapsed calls' own argument rules (both the host and the device call).
+static int check_collapse(const bm25_index* h, int64_t Q, int64_t T, int64_t M, int32_t k,
+                          int32_t per_group) {
+  if (Q < 0 || T < 0 || M < 0) return fail(BM25_EINVAL, "negative query or mask shape");
+  if (k > kMaxK)
+    return fail(BM25_EINVAL,
+                "k=%d: a collapsed search is limited to k <= %d (the per-row group table lives "
+                "in LDS)",
+                k, kMaxK);
+  if (per_group < 1) return fail(BM25_EINVAL, "per_group=%d must be >= 1", per_group);
+  return check_k(h, k);
+}
+
+int bm25_search_collapsed(bm25_index* h, const int32_t* queries, const float* weights, int64_t Q,
+                          int64_t T, int32_t k, const uint32_t* masks, int64_t M,
+                          const int32_t* query_mask, const int32_t* groups, int32_t per_group,
+                          int32_t* out_docs, float* out_scores, int32_t* out_groups) {
+  if (!h) return fail(BM25_EINVAL, "NULL index");
+  int rc = check_collapse(h, Q, T, M, k, per_group);
+  if (rc) return rc;
+  if (Q == 0 || k == 0) return BM25_OK;
+  if (T > 0 && !queries) return fail(BM25_EINVAL, "NULL queries");
+  if (M > 0 && !masks) return fail(BM25_EINVAL, "NULL masks");
+  if (!groups) return fail(BM25_EINVAL, "NULL groups (one int32 per document; < 0: no group)");
+  if (!out_docs || !out_scores) return fail(BM25_EINVAL, "NULL output");
+  rc = check_token_ids(h->ix.n_terms, 0, queries, Q * T);
+  if (rc) return rc;
+  if (weights) {
+    rc = check_weights(queries, weights, Q, T);
+    if (rc) return rc;
+  }
+  if (query_mask)
+    for (int64_t i = 0; i < Q; ++i)
+      if (query_mask[i] < -1 || query_mask[i] >= M)
+        return fail(BM25_EINVAL, "query_mask[%lld] = %d is outside [-1, %lld)", (long long)i,
+                    query_mask[i], (long long)M);
+  Enter in(h);
+  if (in.rc) return in.rc;
+  rc = ensure_io(h, Q * T, Q * (int64_t)k);
+  if (rc) return rc;
+  // the weights, masks, mask ids, groups and the rows' groups: staging buffers
+  // of this call's own
+  const int64_t W = (h->ix.n_docs + 31) >> 5;
+  HostCall c(h->stream);
+  float* d_w = weights ? c.alloc<float>(Q * T) : nullptr;
+  uint32_t* d_masks = M > 0 ? c.alloc<uint32_t>(M * W) : nullptr;
+  int32_t* d_qm = query_mask ? c.alloc<int32_t>(Q) : nullptr;
+  if (weights) c.upload_to(d_w, weights, Q * T);
+  c.upload_to(d_masks, masks, M * W);
+  if (query_mask) c.upload_to(d_qm, query_mask, Q);
+  const int32_t* d_groups = c.upload(groups, h->ix.n_docs);
+  int32_t* d_og = c.alloc<int32_t>(Q * (int64_t)k);
+  c.upload_to(h->d_q, queries, Q * T);
+  if (!c.ok()) return c.finish("collapsed search staging");
+  c.hold(run_collapsed(h, h->d_q, d_w, Q, T, k, d_masks, M, d_qm, d_groups, per_group, h->d_docs,
+                       h->d_scores, d_og, h->stream));
+  c.download(out_docs, h->d_docs, Q * k);
+  c.download(out_scores, h->d_scores, Q * k);
+  if (out_groups) c.download(out_groups, d_og, Q * k);
+  return c.finish("collapsed search");
+}
+
+int bm25_search_collapsed_device(bm25_index* h, const int32_t* d_queries, const float* d_weights,
+                                 int64_t Q, int64_t T, int32_t k, const uint32_t* d_masks,
+                                 int64_t M, const int32_t* d_query_mask, const int32_t* d_groups,
+                                 int32_t per_group, int32_t* d_docs, float* d_scores,
+                                 int32_t* d_groups_out, void* stream) {
+  if (!h) return fail(BM25_EINVAL, "NULL index");
+  int rc = check_collapse(h, Q, T, M, k, per_group);
+  if (rc) return rc;
+  if (Q == 0 || k == 0) return BM25_OK;
+  if (T > 0 && !d_queries) return fail(BM25_EINVAL, "NULL queries");
+  if (M > 0 && !d_masks) return fail(BM25_EINVAL, "NULL masks");
+  if (!d_groups) return fail(BM25_EINVAL, "NULL groups (one int32 per document; < 0: no group)");
+  if (!d_docs || !d_scores) return fail(BM25_EINVAL, "NULL output");
+  Enter in(h);
+  if (in.rc) return in.rc;
+  return run_collapsed(h, d_queries, d_weights, Q, T, k, d_masks, M, d_query_mask, d_groups,
+                       per_group, d_docs, d_scores, d_groups_out, (hipStream_t)stream);
+}
+
+int bm25_search_collapsed_stats(bm25_index* h, int64_t* out, int32_t n) {
+  if (!h) return fail(BM25_EINVAL, "NULL index");
+  if (!out) return fail(BM25_EINVAL, "NULL argument");
+  if (n < 1 || n > 4) return fail(BM25_EINVAL, "n=%d must be in 1..4", n);
+  std::lock_guard<std::mutex> lk(h->mu);
+  for (int i = 0; i < n; ++i) out[i] = h->cstats[i];
+  return BM25_OK;
 }
 
 int bm25_search_filtered_stats(bm25_index* h, int64_t* out, int32_t n) {

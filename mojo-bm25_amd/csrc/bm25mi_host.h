@@ -141,6 +141,10 @@ inline constexpr OptDesc kOptsMore[] = {
     {"row_skip", "BM25_ROW_SKIP", &SearchOpts::row_skip, kOptBool, 0, 1, 0, nullptr},
     {"row_mask_kb", "BM25_ROW_MASK_KB", &SearchOpts::row_mask_kb, kOptRange, 0, 1 << 30, 2,
      nullptr},
+    {"collapse_page", "BM25_COLLAPSE_PAGE", &SearchOpts::collapse_page, kOptRange, 0, kMaxK, 2,
+     nullptr},
+    {"collapse_chunk", "BM25_COLLAPSE_CHUNK", &SearchOpts::collapse_chunk, kOptRange, 0, 1 << 30, 1,
+     "collapse_chunk must be in 0..2^30"},
 };
 
 // Sets / reads one option by name (EINVAL names the accepted values).

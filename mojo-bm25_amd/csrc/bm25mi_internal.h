@@ -99,6 +99,10 @@ struct SearchOpts {
                            // postings all lie in dead sub-blocks (needs seg_skip and rowmask)
   int row_mask_kb = 262144;  // budget of the row-mask table in KiB, read at index build: the
                            // lightest heavy terms past it get no slot and keep all their rows
+  int collapse_page = 0;   // collapsed search: results per page of a round (0: auto; clamped to
+                           // [1, min(n_docs, kMaxK)])
+  int collapse_chunk = 0;  // ... rows per sub-batch of the rounds under exclusion masks (0: auto,
+                           // <= 1 GiB of mask words)
 };
 
 // What the last search launched (bm25_search_dispatch).
@@ -118,6 +122,7 @@ enum {
   kKTileSkip = 32768,  // tile_skip_kernel: the tile bounds' pre-pass of a flat REST launch
   kKSegSkip = 65536,   // (a flag) ... and it marked the dead term segments of scored tiles
   kKRowSkip = 131072,  // (a flag) ... and the dead rows of the heavy terms' kept segments
+  kKCollapsed = 262144,  // (a flag) the search came through bm25_search_collapsed(_device)
 };
 struct Dispatch {
   uint32_t kernels = 0;       // kK* bits of the score kernels launched
@@ -615,6 +620,47 @@ hipError_t launch_range_masks(const DevIndex& ix, const void* d_values, int kind
                               const int32_t* d_fields, const void* d_lo, const void* d_hi,
                               int64_t C, int64_t M, const uint32_t* d_base, int64_t Mb,
                               uint32_t* d_out, hipStream_t stream);
+
+// Field collapsing (bm25mi_collapse.hip; the loop is run_collapsed of
+// bm25mi_capi.cpp).  State by row q of the call: d_count[q] hits kept so far
+// in d_docs / d_scores / d_out_groups [Q][k], and the row's next cursor
+// (d_cur_scores[q], d_cur_docs[q]) — a doc of -1: the row is finished, and
+// every kernel below leaves such a row alone; before the first page the
+// cursors' docs are < -1 and the counts 0.
+//   launch_collapse_page: rows r < R of a batch of pages ([R][p] global docs
+//     and scores in rank order, padded as the cursor search pads) walked into
+//     rows d_row_map[r] (null: r) under groups [n_docs] and per_group; the
+//     rest of a row that finished short of k is padded (doc -1, score bits ~0,
+//     group -1).  d_ctr[0] += rows left unfinished, d_ctr[1] += over-quota page
+//     entries ahead of a row's last kept one (plain sums).  k <= kMaxK.
+//   launch_collapse_compact: d_rows[0 .. U) = the unfinished rows, ascending.
+//   launch_collapse_gather: compact rows r < R (rows d_rows[r]): their queries
+//     [R][T], weights (when d_weights), cursors and mask ids (r).
+//   launch_collapse_exclude: d_excl[R][W] = row d_rows[r]'s own mask (d_masks
+//     [M][W] by d_query_mask, as the filtered search reads them; all ones
+//     without one) minus every document of a group with per_group kept hits;
+//     zeros for a finished row.  Every word is written, bits at or past n_docs
+//     are 0, no word at index >= W of a row and no d_groups entry at index >=
+//     n_docs is touched.
+int collapse_slots(int k);  // slots of the LDS group table at k (8 B each)
+hipError_t launch_collapse_page(const int32_t* d_page_docs, const float* d_page_scores, int32_t p,
+                                const int32_t* d_row_map, int64_t R, const int32_t* d_groups,
+                                int64_t n_docs, int64_t doc_offset, int32_t per_group, int32_t k,
+                                int32_t* d_count, int32_t* d_docs, float* d_scores,
+                                int32_t* d_out_groups, float* d_cur_scores, int32_t* d_cur_docs,
+                                unsigned long long* d_ctr, hipStream_t stream);
+hipError_t launch_collapse_compact(const int32_t* d_cur_docs, int64_t Q, int32_t* d_rows,
+                                   hipStream_t stream);
+hipError_t launch_collapse_gather(const int32_t* d_rows, int64_t R, const int32_t* d_queries,
+                                  const float* d_weights, int64_t T, const float* d_cur_scores,
+                                  const int32_t* d_cur_docs, int32_t* d_cq, float* d_cw,
+                                  float* d_as, int32_t* d_ad, int32_t* d_ids, hipStream_t stream);
+hipError_t launch_collapse_exclude(const int32_t* d_rows, int64_t R, const uint32_t* d_masks,
+                                   int64_t M, const int32_t* d_query_mask, const int32_t* d_groups,
+                                   int64_t n_docs, int32_t per_group, int32_t k,
+                                   const int32_t* d_count, const int32_t* d_out_groups,
+                                   const int32_t* d_cur_docs, uint32_t* d_excl,
+                                   hipStream_t stream);
 
 // Largest token id of [n] device ids (0 if none is positive) into *d_out.
 hipError_t launch_max_token(const int32_t* d_queries, int64_t n, int32_t* d_out,
