@@ -488,8 +488,9 @@ int bm25_search_after_device(bm25_index* idx, const int32_t* d_queries, const fl
  * Doc shards: groups are by the handle's own documents and the ids come back
  * global.  A document of the collection's collapsed top-k is inside its
  * shard's collapsed top-k, so the shards' (doc, score, group) lists merged in
- * key order and collapsed once more are exact; bm25mi.dist does
- * not do this yet.
+ * key order and collapsed once more are exact:
+ * bm25_merge_collapsed_device below does that on the device, and
+ * bm25mi.dist.sharded_search_collapsed is the search on top of it.
  * How: rounds.  Round 1 is one cursor-search page of p results for every row
  * (option "collapse_page"), walked in rank order against the row's group
  * counters.  The rows that are neither full nor out of documents go on in
@@ -862,6 +863,61 @@ int bm25_merge_sorted_device(int device, const int32_t* d_docs,
                              const float* d_scores, int64_t W, int64_t Q,
                              int32_t k, int64_t rank_stride, int32_t* d_out_docs,
                              float* d_out_scores, void* stream);
+
+/*
+ * The merge of collapsed searches over doc shards: the W-way merge of
+ * bm25_merge_sorted_device with the walk of bm25_search_collapsed run over the
+ * merged order, so the quota holds across shards (two shards can each return a
+ * hit of one group; a plain merge of collapsed lists would keep both).
+ * Replaces no reference call: the reference is single-device (main.py:205) and
+ * BM25v.search has no grouping (bm25_native.py:76-158).
+ *   d_docs / d_scores / d_groups: list w of row q starts at element
+ *              w * rank_stride + q * k of each of the three pointers:
+ *              rank_stride = Q * k for plain [W, Q, k] arrays; 3 * Q * k, with
+ *              the pointers Q * k apart, for the packed
+ *              [W][docs|scores|groups][Q][k] buffer that one all-gather moves.
+ *              Each list is what bm25_search_collapsed(_device) writes with
+ *              out_groups: global doc ids, strictly in result order (score
+ *              descending, doc ascending, by the engine's key), real entries
+ *              first; the first doc < 0 and everything after it is padding and
+ *              is never read into a result.  A negative group on a real entry
+ *              means "no group".  Doc ids are unique across the lists.
+ *   Row q of the outputs [Q, k]: the first k kept entries of the walk of the
+ *              merged order under per_group (the walk rule of
+ *              bm25_search_collapsed: an entry without a group is always kept,
+ *              one of group g iff fewer than per_group of g were kept before
+ *              it), as (doc, score bits, group); padding is doc -1, score bits
+ *              0xFFFFFFFF, group -1.  Every output slot is written.
+ *              d_out_groups may be NULL (not wanted).
+ * Identities:
+ *   every input a shard's collapsed list at the same k and per_group (masks and
+ *              weights included): the output is bit for bit the single-index
+ *              bm25_search_collapsed row over the collection;
+ *   per_group >= k, or all groups negative: docs and scores are bit for bit
+ *              those of bm25_merge_sorted_device on the same lists;
+ *   W = 1 returns its input (padding made canonical).
+ * Errors (BM25_EINVAL, the message names the value, checked before any device
+ * call): W < 1 or W > 64 (merge wider worlds in stages), negative Q or k,
+ * k > 4096 (the group table lives in LDS, as bm25_search_collapsed's),
+ * per_group < 1, rank_stride < Q * k, a NULL input or output pointer with a
+ * non-empty shape (d_out_groups alone may be NULL).  k == 0 or Q == 0: BM25_OK
+ * without device work.  Q may pass 65535.
+ * A list that breaks the order precondition gives that row unspecified
+ * contents: the other rows are unaffected, nothing outside the caller's
+ * buffers is touched, and the kernel ends (at most W * k + 1 rounds a row).
+ * How: one wavefront per row, in rounds: a window of every list (W * B <= 512
+ * keys, B = 64 at W <= 8 down to 8 at W = 64), the window entries at or above
+ * the best last window key of the lists that go on are next in the merged
+ * order; they are ranked by binary searches of the other windows and walked
+ * 64 at a time against the row's group table in LDS.  No scratch, no atomics
+ * on global memory, no host synchronisation; enqueued on `stream`.
+ * Not a search: it takes no handle and leaves every handle's dispatch and
+ * stats alone.
+ */
+int bm25_merge_collapsed_device(int device, const int32_t* d_docs, const float* d_scores,
+                                const int32_t* d_groups, int64_t W, int64_t Q, int32_t k,
+                                int64_t rank_stride, int32_t per_group, int32_t* d_out_docs,
+                                float* d_out_scores, int32_t* d_out_groups, void* stream);
 
 /*
  * Doc-sharded search with a GLOBAL threshold, one rank per GPU (the

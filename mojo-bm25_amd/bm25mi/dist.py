@@ -339,3 +339,83 @@ def sharded_search(index, d_queries: torch.Tensor, k: int, shard_docs_max: int,
         merge_sorted_device(d_queries.device.index, g, g[:, 1].view(torch.float32), world, Q, k,
                             2 * Q * k, d_docs, d_scores, stream)
         return d_docs, d_scores
+
+
+def sharded_search_collapsed(index, d_queries: torch.Tensor, k: int, d_groups: torch.Tensor,
+                             per_group: int = 1, d_weights: Optional[torch.Tensor] = None,
+                             d_masks: Optional[torch.Tensor] = None,
+                             d_query_mask: Optional[torch.Tensor] = None,
+                             d_docs: Optional[torch.Tensor] = None,
+                             d_scores: Optional[torch.Tensor] = None,
+                             d_groups_out: Optional[torch.Tensor] = None, stream=None,
+                             group: Optional[dist.ProcessGroup] = None
+                             ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """One rank's collapsed search over doc shards (field collapsing: at most
+    ``per_group`` hits of a group in a row's top-k): exactly the single-index
+    GpuIndex.search_collapsed over the whole collection, on every rank.
+
+    Every rank runs search_collapsed_device on its shard — ``d_groups``,
+    ``d_masks`` and ``d_weights`` are by the rank's own documents, as that call
+    documents them — into one packed int32 [3, Q, k] buffer (docs | score bits
+    | groups).  One all-gather moves it (12 Q k bytes per rank), and
+    bm25_merge_collapsed_device merges the world's lists in key order while it
+    collapses them once more: a document of the collection's collapsed top-k
+    is inside its shard's collapsed top-k, and a merged entry that the
+    collection drops finds its per_group better group-mates in the merged input
+    (DESIGN.md §4).  A plain merge would not do: two shards can each return a
+    hit of one group.
+
+    A shard of fewer than k documents searches at min(k, n_docs) and pads its
+    slice.  World size 1 is the plain call, no collective.  Everything is
+    enqueued on ``stream`` (default: the current stream), the merge after the
+    all-gather as in sharded_search; the shard's search synchronises the
+    stream once per round.  Returns (docs, scores, groups), each [Q, k]."""
+    if d_queries.dim() != 2:
+        raise ValueError("d_queries must be a 2-D [Q, T] tensor")
+    k, per_group = int(k), int(per_group)
+    if k < 0:
+        raise ValueError(f"k={k} must be >= 0")
+    world = dist.get_world_size(group)
+    dev = d_queries.device
+    Q = d_queries.shape[0]
+    if d_docs is None:
+        d_docs = torch.empty((Q, k), dtype=torch.int32, device=dev)
+    if d_scores is None:
+        d_scores = torch.empty((Q, k), dtype=torch.float32, device=dev)
+    if d_groups_out is None:
+        d_groups_out = torch.empty((Q, k), dtype=torch.int32, device=dev)
+    for name, t in (("d_docs", d_docs), ("d_scores", d_scores), ("d_groups_out", d_groups_out)):
+        if t.numel() != Q * k or t.element_size() != 4 or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous 32-bit [{Q}, {k}] tensor")
+    if dev.type != "cuda":
+        stream = None
+    elif stream is None:
+        stream = torch.cuda.current_stream(dev)
+    elif not isinstance(stream, torch.cuda.Stream):
+        stream = torch.cuda.ExternalStream(int(stream), device=dev)
+    if world == 1:
+        index.search_collapsed_device(d_queries, k, d_groups, per_group, d_weights, d_masks,
+                                      d_query_mask, d_docs, d_scores, d_groups_out, stream)
+        return d_docs, d_scores, d_groups_out
+    from .index import merge_collapsed_device
+    with _stream_ctx(stream):
+        pk = torch.empty((3, Q, k), dtype=torch.int32, device=dev)
+        ks = min(k, int(index.n_docs))  # (the C call rejects k > n_docs)
+        if ks == k:
+            part = pk
+        else:  # a short shard: its [Q, ks] lists, then padding up to k
+            part = torch.empty((3, Q, ks), dtype=torch.int32, device=dev)
+            pk[0].fill_(-1)
+            pk[1].fill_(-1)  # (score bits 0xFFFFFFFF)
+            pk[2].fill_(-1)
+        index.search_collapsed_device(d_queries, ks, d_groups, per_group, d_weights, d_masks,
+                                      d_query_mask, part[0], part[1].view(torch.float32), part[2],
+                                      stream)
+        if ks != k:
+            pk[:, :, :ks].copy_(part)
+        g = _all_gather(pk, group)  # [W, 3, Q, k]: one collective for docs, scores and groups
+        assert tuple(g.shape) == (world, 3, Q, k) and g.is_contiguous(), tuple(g.shape)
+        # the merge reads rank w's docs at w * 3Qk, its scores Qk and its groups 2Qk later
+        merge_collapsed_device(dev.index, g, g[:, 1].view(torch.float32), g[:, 2], world, Q, k,
+                               3 * Q * k, per_group, d_docs, d_scores, d_groups_out, stream)
+    return d_docs, d_scores, d_groups_out

@@ -1410,6 +1410,22 @@ def merge_sorted_device(device: int, d_docs, d_scores, W: int, Q: int, k: int, r
                                        ctypes.c_void_p(s)))
 
 
+def merge_collapsed_device(device: int, d_docs, d_scores, d_groups, W: int, Q: int, k: int,
+                           rank_stride: int, per_group: int, d_out_docs, d_out_scores,
+                           d_out_groups=None, stream=None) -> None:
+    """The doc-shard merge of collapsed lists (bm25_merge_collapsed_device): W
+    best-first [Q, k] lists of (doc, score, group) — what search_collapsed_device
+    writes with d_groups_out — merged in key order and walked once more under
+    per_group.  Rank w's lists start at element w * rank_stride of d_docs /
+    d_scores / d_groups; d_out_groups is optional."""
+    s = getattr(stream, "cuda_stream", stream) or 0
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)
+    check(lib.bm25_merge_collapsed_device(int(device), ptr(d_docs), ptr(d_scores), ptr(d_groups),
+                                          int(W), int(Q), int(k), int(rank_stride), int(per_group),
+                                          ptr(d_out_docs), ptr(d_out_scores), ptr(d_out_groups),
+                                          ctypes.c_void_p(s)))
+
+
 class ShardedIndex:
     """A CSC index doc-sharded over several GPUs of this process
     (bm25_sharded_* in include/bm25mi.h): ``search`` has GpuIndex.search's

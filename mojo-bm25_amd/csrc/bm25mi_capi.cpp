@@ -2362,6 +2362,37 @@ int bm25_merge_sorted_device(int device, const int32_t* d_docs, const float* d_s
   return BM25_OK;
 }
 
+// Every check precedes hipSetDevice: a bad call touches no device.
+int bm25_merge_collapsed_device(int device, const int32_t* d_docs, const float* d_scores,
+                                const int32_t* d_groups, int64_t W, int64_t Q, int32_t k,
+                                int64_t rank_stride, int32_t per_group, int32_t* d_out_docs,
+                                float* d_out_scores, int32_t* d_out_groups, void* stream) {
+  if (W < 1 || W > 64)
+    return fail(BM25_EINVAL, "merge_collapsed: W=%lld must be in 1..64 (W > 64: merge in stages)",
+                (long long)W);
+  if (Q < 0) return fail(BM25_EINVAL, "merge_collapsed: Q=%lld must be >= 0", (long long)Q);
+  if (k < 0) return fail(BM25_EINVAL, "merge_collapsed: k=%d must be >= 0", k);
+  if (k > kMaxK)
+    return fail(BM25_EINVAL,
+                "merge_collapsed: k=%d: collapse is limited to k <= %d (the group table lives in LDS)",
+                k, kMaxK);
+  if (per_group < 1)
+    return fail(BM25_EINVAL, "merge_collapsed: per_group=%d must be >= 1", per_group);
+  if (Q > 0x7FFFFFFF)
+    return fail(BM25_EINVAL, "merge_collapsed: Q=%lld must be < 2^31", (long long)Q);
+  if (rank_stride < Q * (int64_t)k)
+    return fail(BM25_EINVAL, "merge_collapsed: rank_stride=%lld must be >= Q * k (%lld)",
+                (long long)rank_stride, (long long)(Q * (int64_t)k));
+  if (Q == 0 || k == 0) return BM25_OK;
+  if (!d_docs || !d_scores || !d_groups) return fail(BM25_EINVAL, "merge_collapsed: NULL input");
+  if (!d_out_docs || !d_out_scores) return fail(BM25_EINVAL, "merge_collapsed: NULL output");
+  HIP_TRY(hipSetDevice(device), "hipSetDevice");
+  HIP_TRY(launch_merge_collapsed(d_docs, d_scores, d_groups, W, Q, k, rank_stride, per_group,
+                                 d_out_docs, d_out_scores, d_out_groups, (hipStream_t)stream),
+          "merge_collapsed launch");
+  return BM25_OK;
+}
+
 int bm25_profile_enable(bm25_index* h, int on) {
   if (!h) return fail(BM25_EINVAL, "NULL index");
   std::lock_guard<std::mutex> lk(h->mu);

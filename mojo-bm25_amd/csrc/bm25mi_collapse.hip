@@ -19,10 +19,15 @@
 //   collapse_exclude_kernel  the compact rows' allow-masks: the row's own mask
 //                            minus every document of a saturated group
 //
+// The group table and the step that decides a 64-entry chunk live in
+// bm25mi_collapse_dev.h, shared with the doc-shard merge
+// (bm25mi_merge_collapse.hip).
+//
 // Nothing here depends on scheduling: a row is one wave's, the lanes of a
 // chunk decide from ballots, LDS atomics only insert keys and sum counts (the
 // lookups read the same values whatever the order), and the two global
 // counters are plain sums.  Plain C++ and vector memory operations throughout.
+#include "bm25mi_collapse_dev.h"
 #include "bm25mi_internal.h"
 
 #include <algorithm>
@@ -34,42 +39,6 @@ namespace {
 constexpr int kExT = 256;          // threads of the exclusion kernel: 4 waves, 64 words each
 constexpr int kExStepWords = 256;  // mask words of a workgroup's step
 constexpr int kCompactT = 1024;    // threads of the compaction kernel
-
-// The group table: `slots` (a power of two, >= 2 * the keys it may hold) int32
-// keys, -1 = empty, then `slots` int32 counts.  Linear probing from a
-// multiplicative hash.
-__device__ inline uint32_t tab_home(int32_t g, int lg) {
-  return ((uint32_t)g * 0x9E3779B1u) >> (32 - lg);
-}
-
-__device__ inline void tab_clear(int32_t* tab, int slots, int t, int nt) {
-  for (int i = t; i < slots; i += nt) {
-    tab[i] = -1;
-    tab[slots + i] = 0;
-  }
-}
-
-// Adds one to g's count (g >= 0), inserting it when new.
-__device__ inline void tab_add(int32_t* tab, int slots, int lg, int32_t g) {
-  uint32_t s = tab_home(g, lg);
-  for (;;) {
-    const int32_t was = atomicCAS(&tab[s], -1, g);
-    if (was == -1 || was == g) break;
-    s = (s + 1u) & (uint32_t)(slots - 1);
-  }
-  atomicAdd(&tab[slots + s], 1);
-}
-
-// g's count (0 when absent; g >= 0).
-__device__ inline int32_t tab_count(const int32_t* tab, int slots, int lg, int32_t g) {
-  uint32_t s = tab_home(g, lg);
-  for (;;) {
-    const int32_t key = tab[s];
-    if (key == g) return tab[slots + s];
-    if (key == -1) return 0;
-    s = (s + 1u) & (uint32_t)(slots - 1);
-  }
-}
 
 // One wave per row r of a batch of pages (row q = row_map[r] of the call, or r
 // itself).  A row whose cursor says "exhausted" was finished by an earlier
@@ -87,7 +56,6 @@ __global__ __launch_bounds__(64) void collapse_page_kernel(
   const int64_t q = row_map ? row_map[r] : r;
   if (cur_docs[q] == -1) return;  // (block-uniform, before the barriers)
   const int lane = threadIdx.x;
-  const uint64_t below = (1ull << lane) - 1ull;
   int32_t cnt = count[q];
   int32_t* od = out_docs + q * k;
   float* os = out_scores + q * k;
@@ -111,38 +79,19 @@ __global__ __launch_bounds__(64) void collapse_page_kernel(
     ended = __builtin_amdgcn_ballot_w64(i < p && !real) != 0ull;
     const float s = real ? ps[i] : 0.f;
     const int32_t g = real ? groups[dl] : -1;
-    // the lower lanes of the chunk in the same group: the first of a group's
-    // lanes are the ones kept, so a lane is kept iff its rank among them, past
-    // the group's count so far, is below the quota
-    int32_t same = 0;
-    uint64_t todo = __builtin_amdgcn_ballot_w64(real && g >= 0);
-    while (todo) {
-      const int l = (int)__builtin_ctzll(todo);
-      const int32_t gl = __shfl(g, l);
-      const uint64_t m = __builtin_amdgcn_ballot_w64(real && g == gl);
-      if (real && g == gl) same = (int32_t)__popcll(m & below);
-      todo &= ~m;
-    }
-    const bool keep =
-        real && (g < 0 || (int64_t)tab_count(tab, slots, lg, g) + same < (int64_t)per_group);
-    const uint64_t km = __builtin_amdgcn_ballot_w64(keep);
-    const int32_t pos = cnt + (int32_t)__popcll(km & below);
-    const bool take = keep && pos < k;
+    const ChunkStep c = chunk_step(tab, slots, lg, real, g, per_group, cnt, k, lane);
     // over-quota entries ahead of the chunk's last taken entry (all of them
     // when the row does not fill here)
-    const uint64_t tm = __builtin_amdgcn_ballot_w64(take);
-    const int32_t total = cnt + (int32_t)__popcll(km);
-    const uint64_t ahead = total >= k && tm ? (1ull << (63 - __builtin_clzll(tm))) - 1ull : ~0ull;
-    dropped += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(real && !keep) & ahead);
-    __syncthreads();  // (the lookups above, before the table changes)
-    if (take) {
-      od[pos] = d;
-      os[pos] = s;
-      og[pos] = g;
-      if (g >= 0) tab_add(tab, slots, lg, g);
+    const uint64_t ahead =
+        c.total >= k && c.tm ? (1ull << (63 - __builtin_clzll(c.tm))) - 1ull : ~0ull;
+    dropped += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(real && !c.keep) & ahead);
+    if (c.take) {
+      od[c.pos] = d;
+      os[c.pos] = s;
+      og[c.pos] = g;
     }
-    __syncthreads();
-    cnt = min(total, k);
+    chunk_commit(tab, slots, lg, c.take, g);  // (the lookups above, before the table changes)
+    cnt = min(c.total, k);
   }
   const int32_t last = pd[p - 1];
   const bool done = cnt >= k || ended || last < 0;

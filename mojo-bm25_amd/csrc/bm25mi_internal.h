@@ -662,6 +662,17 @@ hipError_t launch_collapse_exclude(const int32_t* d_rows, int64_t R, const uint3
                                    const int32_t* d_cur_docs, uint32_t* d_excl,
                                    hipStream_t stream);
 
+// The doc-shard merge of collapsed lists (bm25mi_merge_collapse.hip;
+// bm25_merge_collapsed_device): W best-first lists [Q, k] of (doc, score,
+// group) at element w * rank_stride of the three inputs, padding (doc < 0)
+// last -> row q = the first k kept entries of the walk of the merged order
+// under per_group, padded (doc -1, score bits ~0, group -1); d_out_groups may
+// be null.  Every output slot is written.  1 <= W <= 64, k <= kMaxK.
+hipError_t launch_merge_collapsed(const int32_t* d_docs, const float* d_scores,
+                                  const int32_t* d_groups, int64_t W, int64_t Q, int32_t k,
+                                  int64_t rank_stride, int32_t per_group, int32_t* d_out_docs,
+                                  float* d_out_scores, int32_t* d_out_groups, hipStream_t stream);
+
 // Largest token id of [n] device ids (0 if none is positive) into *d_out.
 hipError_t launch_max_token(const int32_t* d_queries, int64_t n, int32_t* d_out,
                             hipStream_t stream);
