@@ -818,6 +818,124 @@ int bm25_search_boolean_ranges(bm25_index* idx, const int32_t* queries, int64_t 
                                int64_t* out_total_hits, int64_t* out_facets);
 
 /*
+ * Sort-by-field search: the documents a mask allows in the order of a
+ * per-document column ("newest first", "cheapest first", by tenant id)
+ * instead of by score — the exact top-k of a mask by a column, ties broken by
+ * doc id, independent of scheduling.  Replaces no reference call.
+ *
+ * A column's order does not depend on the query, so the work is split: the
+ * rank build, once per column and direction, and the selection, per batch.
+ *
+ *   Order of a column (kind: BM25_FIELD_I32 / _F32 / _I64, as the range
+ *   filters): int32 and int64 are compared as themselves; int64 never goes
+ *   through a float.  float32 is numeric order with -0.0f == +0.0f, as the
+ *   range filters compare.  NaN is "no value": it comes after every number in
+ *   both directions.  descending != 0 reverses the order of the numbers only;
+ *   NaN stays last.  Equal values are ordered by doc id ascending in both
+ *   directions: +-0, all NaNs and repeated integers included.
+ *
+ *   values  [n_docs]     of `kind`, by the handle's own documents
+ *   ranks   [n_docs] int32  ranks[d] = the rank of document d in that order
+ *   perm    [n_docs] int32  perm[r] = the handle-local document at rank r
+ *   masks   [M, W] uint32, W = ceil(n_docs / 32), the layout of
+ *                        bm25_search_filtered; NULL: every document is allowed
+ *                        for all M rows
+ *   after_ranks [M] int32  row m's cursor, or NULL: no cursor for any row
+ *   out_docs, out_ranks [M, k] int32
+ *
+ * bm25_sort_ranks / bm25_sort_ranks_device: both outputs are permutations of
+ *   [0, n_docs) and inverses of each other.  No values entry at index >=
+ *   n_docs is read; n_docs == 0 returns BM25_OK without device work.  Ranks
+ *   are unique 32-bit keys that already contain the direction, the dtype's
+ *   comparison, the NaN rule and the doc-id tie-break.  The device call is a
+ *   setup call, like bm25_index_set_world_bounds: it allocates and frees a
+ *   buffer of its own — the sort's key/value double buffers, 24 bytes per
+ *   document, and its histogram, 1 KiB per 4096 documents — and synchronises
+ *   `stream` before it returns.  It reads the caller's buffers only and is
+ *   not a search.  BM25_EINVAL for a NULL index, a bad kind, or NULL pointers
+ *   with n_docs > 0.
+ *
+ * bm25_search_sorted / bm25_search_sorted_device: document d is eligible for
+ *   row m iff mask m allows it and ranks[d] > after_ranks[m].  Row m of the
+ *   outputs is the k eligible documents of smallest rank, in rank order, as
+ *   (perm[rank] + doc_offset, rank); where fewer are eligible the rest of the
+ *   row is padding: doc -1 and rank -1.  Without masks row m is
+ *   perm[after + 1 .. after + k].  Bits at or past n_docs are ignored, and no
+ *   word at index >= W of a row is read.
+ *   Cursors: after_ranks[m] == BM25_AFTER_NONE (-2), or a NULL pointer, means
+ *   no cursor.  -1 is the rank of a padding slot: the row is all padding and
+ *   reads no mask word, so feeding back any page's last column is always
+ *   safe.  Entries < -2 are "no cursor" in the device call and BM25_EINVAL in
+ *   the host call.  The last column of out_ranks is the next page's cursor.
+ *   0 <= k <= min(n_docs, 4096); k > 4096 is BM25_EINVAL, the limit of the
+ *   collapsed search, for the same LDS reason (a row's list is sorted in one
+ *   workgroup's LDS).  k == 0 or M == 0 returns BM25_OK without device work.
+ *   M may pass 65535.  The result is integer and depends neither on
+ *   scheduling nor on any option; the global atomics are integer adds.
+ *   Host call: validated, synchronous.  It checks that ranks and perm are
+ *   inverse permutations (the message names the first offending index),
+ *   shapes, NULLs and cursor entries.  On an error the outputs are untouched.
+ *   Device call: it checks shapes, NULLs, k, and scratch_bytes against
+ *   bm25_search_sorted_scratch (scratch 4-byte aligned; none is needed
+ *   without masks).  It never synchronises and retains nothing.  It reads
+ *   only the caller's buffers and writes only the outputs and d_scratch.  It
+ *   is not ordered against the handle's searches.  It leaves
+ *   bm25_search_dispatch, the counters and bm25_search_filtered_stats alone.
+ *   A ranks entry outside [0, n_docs) is never eligible.  With arrays that
+ *   are not inverse permutations the affected rows are unspecified, and
+ *   nothing outside the caller's buffers is touched.
+ *   Method: a row's rank interval, [0, n_docs) at first, is narrowed by
+ *   histograms over rank bits — a pass over the mask words and ranks counts
+ *   the row's eligible documents per bin of its interval, the interval
+ *   becomes the bin that holds the k-th — until it is at most Wmax = 2048
+ *   ranks wide; one more pass lists every eligible rank below the interval's
+ *   end (fewer than k below it, at most Wmax inside), the list is sorted and
+ *   its first k written.  levels + 1 passes over the masks, no fallback path.
+ * bm25_search_sorted_scratch: *bytes = 4 M (4 + 1 + 256 + min(k + 2048,
+ *   n_docs)): per row the interval state, the list count, the histogram of at
+ *   most 256 bins and the list.  The same k and M rules (BM25_EINVAL).
+ * Option "sorted_bins" (below) sets the bins per level.
+ *
+ * bm25_search_boolean_sorted: every argument of bm25_search_boolean_ranges,
+ *   then (ranks, perm, after_ranks [Q], out_ranks [Q, k]).  With ranks == NULL
+ *   it is bm25_search_boolean_ranges, bit for bit, chunk size included.  With
+ *   ranks, each chunk's mask is built exactly as there — range AND terms AND
+ *   base — and totals and facets are taken of it; rows are then selected by
+ *   rank instead of by score.  out_scores[q][j] is bm25_score_docs_device's
+ *   bits for (queries[q], hit j).  Padding slots are doc -1, score bits
+ *   0xFFFFFFFF and rank -1, the padding of every other search.  ranks and
+ *   perm (validated as bm25_search_sorted validates them) go up once per
+ *   call, as the groups and columns do; the masks still never move to the
+ *   host.  k > 4096 with ranks is BM25_EINVAL.
+ *
+ * Out of scope: merging sorted lists of doc shards (ranks are per handle, so
+ * a shard merge needs (value, doc) keys); secondary sort keys other than doc
+ * id; an early-terminating walk of perm for dense masks; k > 4096.
+ */
+int bm25_sort_ranks(bm25_index* idx, const void* values, int32_t kind, int32_t descending,
+                    int32_t* out_ranks, int32_t* out_perm);
+int bm25_sort_ranks_device(bm25_index* idx, const void* d_values, int32_t kind, int32_t descending,
+                           int32_t* d_ranks, int32_t* d_perm, void* stream);
+int bm25_search_sorted_scratch(const bm25_index* idx, int64_t M, int32_t k, int64_t* bytes);
+int bm25_search_sorted(bm25_index* idx, const uint32_t* masks, int64_t M, const int32_t* ranks,
+                       const int32_t* perm, int32_t k, const int32_t* after_ranks,
+                       int32_t* out_docs, int32_t* out_ranks);
+int bm25_search_sorted_device(bm25_index* idx, const uint32_t* d_masks, int64_t M,
+                              const int32_t* d_ranks, const int32_t* d_perm, int32_t k,
+                              const int32_t* d_after_ranks, int32_t* d_docs, int32_t* d_out_ranks,
+                              void* d_scratch, int64_t scratch_bytes, void* stream);
+int bm25_search_boolean_sorted(bm25_index* idx, const int32_t* queries, int64_t Q, int64_t T,
+                               int32_t k, const int32_t* must, int64_t A, const int32_t* any,
+                               int64_t B, const int32_t* must_not, int64_t N,
+                               const int32_t* min_match, const uint32_t* base, int64_t Mb,
+                               const int32_t* groups, int64_t G, const void* values, int32_t kind,
+                               int64_t F, const int32_t* fields, const void* lo, const void* hi,
+                               int64_t C, int32_t* out_docs, float* out_scores,
+                               int64_t* out_total_hits, int64_t* out_facets, const int32_t* ranks,
+                               const int32_t* perm, const int32_t* after_ranks,
+                               int32_t* out_ranks);
+
+/*
  * bm25.BM25's float64 path (the dense model's API keeps the reference's
  * precision).  bm25_index_set_values_f64 keeps a float64 copy of the index's
  * values beside it (the same CSC order; bm25_build_scores method 1 returns
@@ -1172,6 +1290,9 @@ int bm25_search_counters(bm25_index* idx, int64_t* out, int32_t n);
  *   "collapse_chunk" bm25_search_collapsed: rows per sub-batch of the rounds
  *                    under exclusion masks; 0 (default) = automatic: at most
  *                    1 GiB of mask words per sub-batch, at least one row
+ *   "sorted_bins"    bm25_search_sorted: histogram bins per level of the rank
+ *                    selection, 0..256 (env BM25_SORTED_BINS); 0 (default) or
+ *                    1 = automatic: 256.  Fewer bins take more levels
  *   "grid_pct"      percent of the device's resident workgroup slots the
  *                    persistent score kernels launch (1..100, default 100):
  *                    below 100 leaves slots for kernels of another stream

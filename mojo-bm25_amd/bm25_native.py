@@ -281,7 +281,7 @@ class BM25v:
 
     def search_boolean(self, queries, top_k: int, must=None, any=None, must_not=None,
                        base=None, *, min_match=None, total_hits: bool = False, facets=None,
-                       ranges=None):
+                       ranges=None, sort=None, after_ranks=None):
         """search under boolean term filters (not in the reference, whose
         search has no term filter): query q ranks only the documents that hold
         every term of ``must[q]``, at least one of ``any[q]`` (when it names
@@ -302,7 +302,11 @@ class BM25v:
         field; GpuIndex.range_masks describes them, bm25mi.range_rows makes the
         last three of dicts) also asks, per query, for numeric fields of the
         documents within inclusive bounds: a date or price range, tested on
-        the GPU."""
+        the GPU.  ``sort=(ranks, perm)`` (GpuIndex.sort_ranks makes the pair
+        of a column, once per column and direction) returns each query's hits
+        in that column's order instead of by score — "newest first" — with
+        their int32 [Q, top_k] ranks after the scores; ``after_ranks`` (a
+        page's last ranks column) continues after a page."""
         if facets is not None and (not isinstance(facets, (tuple, list)) or len(facets) != 2):
             raise ValueError("facets must be a pair (groups, n_groups)")
         if ranges is not None and (not isinstance(ranges, (tuple, list))
@@ -311,6 +315,8 @@ class BM25v:
                              "field, a triple (values, lo, hi)")
         if len(queries) == 0:
             empty = np.zeros((0, 0), dtype=self.dtype), np.zeros((0, 0), dtype=self.dtype)
+            if sort is not None:
+                empty += (np.zeros((0, 0), np.int32),)
             if total_hits:
                 empty += (np.zeros(0, np.int64),)
             if facets is not None:
@@ -351,6 +357,10 @@ class BM25v:
             more["facets"] = facets
         if ranges is not None:
             more["ranges"] = ranges
+        if sort is not None:
+            more["sort"] = sort
+        if after_ranks is not None:
+            more["after_ranks"] = after_ranks
         return self._gpu.search_boolean(queries, top_k, clauses[0], clauses[1], clauses[2], base,
                                         min_match=min_match, total_hits=total_hits, **more)
 

@@ -102,6 +102,15 @@ _SIGS = {
     "bm25_search_boolean_ranges": ([_P, _P, _I64, _I64, _I32, _P, _I64, _P, _I64, _P, _I64, _P,
                                     _P, _I64, _P, _I64, _P, _I32, _I64, _P, _P, _P, _I64, _P, _P,
                                     _P, _P], ctypes.c_int),
+    "bm25_sort_ranks": ([_P, _P, _I32, _I32, _P, _P], ctypes.c_int),
+    "bm25_sort_ranks_device": ([_P, _P, _I32, _I32, _P, _P, _P], ctypes.c_int),
+    "bm25_search_sorted_scratch": ([_P, _I64, _I32, _PI64], ctypes.c_int),
+    "bm25_search_sorted": ([_P, _P, _I64, _P, _P, _I32, _P, _P, _P], ctypes.c_int),
+    "bm25_search_sorted_device": ([_P, _P, _I64, _P, _P, _I32, _P, _P, _P, _P, _I64, _P],
+                                  ctypes.c_int),
+    "bm25_search_boolean_sorted": ([_P, _P, _I64, _I64, _I32, _P, _I64, _P, _I64, _P, _I64, _P,
+                                    _P, _I64, _P, _I64, _P, _I32, _I64, _P, _P, _P, _I64, _P, _P,
+                                    _P, _P, _P, _P, _P, _P], ctypes.c_int),
     "bm25_index_set_values_f64": ([_P, _P], ctypes.c_int),
     "bm25_scores_dense_f64": ([_P, _P, _I64, _P], ctypes.c_int),
     "bm25_topn_f64": ([_P, _P, _I64, _I64, _P, _P], ctypes.c_int),

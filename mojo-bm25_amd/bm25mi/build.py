@@ -21,7 +21,7 @@ SYNTH_LIB = os.path.join(PKG_DIR, "libbm25synth.so")
 HIP_SOURCES = ["bm25mi_kernels.hip", "bm25mi_large.hip", "bm25mi_build.hip", "bm25mi_sort.hip",
                "bm25mi_dense.hip", "bm25mi_lookup.hip", "bm25mi_filter.hip", "bm25mi_termmask.hip",
                "bm25mi_facets.hip", "bm25mi_range.hip", "bm25mi_collapse.hip",
-               "bm25mi_merge_collapse.hip", "bm25mi_capi.cpp"]
+               "bm25mi_merge_collapse.hip", "bm25mi_sorted.hip", "bm25mi_capi.cpp"]
 # Every header a source may include: an object older than one of them is stale.
 HEADERS = [os.path.join(CSRC, "bm25mi_internal.h"), os.path.join(CSRC, "bm25mi_host.h"),
            os.path.join(CSRC, "bm25mi_collapse_dev.h"),
@@ -104,6 +104,26 @@ def build_asan_check(verbose: bool = False) -> str:
     _run([hipcc, f"--offload-arch={ARCH}", "-fsanitize=address", "-fno-gpu-sanitize", "-o",
           exe + ".tmp"] + objs, verbose)
     os.replace(exe + ".tmp", exe)
+    return exe
+
+
+def build_sorted_check(verbose: bool = False) -> str:
+    """tests/asan/sorted_check built by the host compiler alone with
+    AddressSanitizer and UBSan (-fsanitize=address,undefined; it includes the
+    host headers, makes no HIP call and links none), into
+    mojo-bm25_amd/bm25mi/_asan/ (rebuilt when a source is newer).  Test
+    infrastructure for tests/test_search_sorted_host.py, not the product."""
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    rocm_inc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(hipcc))), "include")
+    out = os.path.join(PKG_DIR, "_asan")
+    os.makedirs(out, exist_ok=True)
+    exe = os.path.join(out, "sorted_check")
+    main = os.path.join(REPO, "tests", "asan", "sorted_check.cpp")
+    if _stale(exe, [main] + HEADERS):
+        _run(["g++", "-std=c++17", "-O1", "-g", "-w", "-fsanitize=address,undefined",
+              "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-D__HIP_PLATFORM_AMD__",
+              "-I", rocm_inc, "-o", exe + ".tmp", main], verbose)
+        os.replace(exe + ".tmp", exe)
     return exe
 
 

@@ -246,6 +246,85 @@ def _ranges_arg(ranges):
 AFTER_NONE = -2  # BM25_AFTER_NONE: an after-docs entry that means "no cursor"
 
 
+SORTED_MAX_K = 4096  # bm25_search_sorted: hits a row, at most (the LDS sort of a row's list)
+_SORT_KINDS = {np.dtype(np.int32): 0, np.dtype(np.float32): 1, np.dtype(np.int64): 2}
+
+
+def _sort_values_arg(values, n_docs: int):
+    """A sort column: [n_docs] int32, int64 or float32 exactly -> (contiguous
+    array, kind)."""
+    v = np.asarray(values)
+    if v.dtype not in _SORT_KINDS:
+        raise ValueError(f"values have dtype {v.dtype.name}: int32, int64 or float32 (nothing is "
+                         "rounded)")
+    if v.shape != (n_docs,):
+        raise ValueError(f"values has shape {v.shape}, expected ({n_docs},) (one entry per "
+                         "document)")
+    return np.ascontiguousarray(v), _SORT_KINDS[v.dtype]
+
+
+def _order_arg(order, n_docs: int):
+    """order=(ranks, perm), as GpuIndex.sort_ranks returns them -> two
+    contiguous int32 [n_docs] arrays, checked to be inverse permutations (the
+    C call's check and message: the first offending index)."""
+    if not isinstance(order, (tuple, list)) or len(order) != 2:
+        raise ValueError("the order must be a pair (ranks, perm), as sort_ranks returns it")
+    out = []
+    for name, a in zip(("ranks", "perm"), order):
+        a = np.asarray(a)
+        if a.dtype.kind not in "iu" or a.shape != (n_docs,):
+            raise ValueError(f"{name} must be an integer [{n_docs}] array (one entry per "
+                             f"document), got {a.dtype.name} {a.shape}")
+        if a.size and (int(a.min()) < np.iinfo(np.int32).min
+                       or int(a.max()) > np.iinfo(np.int32).max):
+            raise ValueError(f"{name} holds values outside int32")
+        out.append(np.ascontiguousarray(a, dtype=np.int32))
+    ranks, perm = out
+    bad = (ranks < 0) | (ranks >= n_docs)
+    ok = ~bad
+    back = np.full(n_docs, -1, np.int64)
+    back[ok] = perm[ranks[ok]]
+    wrong = np.flatnonzero(bad | (back != np.arange(n_docs)))
+    if wrong.size:
+        d = int(wrong[0])
+        r = int(ranks[d])
+        if bad[d]:
+            raise ValueError(f"ranks[{d}] = {r} is outside [0, {n_docs})")
+        raise ValueError(f"ranks[{d}] = {r} but perm[{r}] = {int(perm[r])}: ranks and perm are "
+                         "not inverse permutations")
+    return ranks, perm
+
+
+def _after_ranks_arg(after, rows: int, what: str = "mask row"):
+    """Cursors of a sorted search: None, or an int [rows] array of ranks, -1 (a
+    padding slot's rank: an all-padding row) or -2 (no cursor)."""
+    if after is None:
+        return None
+    a = np.asarray(after)
+    if a.dtype.kind not in "iu" or a.shape != (rows,):
+        raise ValueError(f"after must hold one rank per {what} ({rows}), got {a.dtype.name} "
+                         f"{a.shape}")
+    a = np.ascontiguousarray(a, dtype=np.int64)
+    low = np.flatnonzero(a < -2)
+    if low.size:
+        m = int(low[0])
+        raise ValueError(f"after_ranks[{m}] = {int(a[m])} is below BM25_AFTER_NONE (-2)")
+    return np.ascontiguousarray(np.minimum(a, np.iinfo(np.int32).max), dtype=np.int32)
+
+
+def _sorted_k(k, n_docs: int) -> int:
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+        raise ValueError("k must be an int")
+    k = int(k)
+    if k < 0:
+        raise ValueError("negative dimensions are not allowed")
+    if k > SORTED_MAX_K:
+        raise ValueError(f"k = {k}: a sorted search returns at most {SORTED_MAX_K} hits a row")
+    if k > n_docs:
+        raise ValueError(f"k = {k} is above the index's {n_docs} documents")
+    return k
+
+
 def page_cursor(docs, scores):
     """The cursor after a page of results: its last column as the pair
     (scores [Q] float32, docs [Q] int32) that search_after's ``after`` takes.
@@ -1204,9 +1283,126 @@ class GpuIndex:
             p(d_lo, M * C), p(d_hi, M * C), C, M, p(d_base, Mb and W), Mb, p(d_out, M and W),
             ctypes.c_void_p(s)))
 
+    # ------------------------------------------------- sort-by-field search
+    def sort_ranks(self, values, descending: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+        """The order of this handle's documents by a column (bm25_sort_ranks,
+        host arrays) -> (ranks, perm), int32 [n_docs] each: perm[r] = the
+        document at rank r, ranks[d] = the rank of document d.  values: [n_docs]
+        int32, int64 or float32 exactly.  Numbers in numeric order (-0.0 equals
+        +0.0; int64 never through a float), reversed by ``descending``; NaN
+        after every number in both directions; equal values by doc id
+        ascending.  Built once per column and direction, the pair is the
+        ``order`` of search_sorted and the ``sort`` of search_boolean."""
+        v, kind = _sort_values_arg(values, self.n_docs)
+        ranks = np.zeros(self.n_docs, np.int32)
+        perm = np.zeros(self.n_docs, np.int32)
+        check(lib.bm25_sort_ranks(self._h, _ptr(v) if v.size else None, kind,
+                                  1 if descending else 0, _ptr(ranks) if v.size else None,
+                                  _ptr(perm) if v.size else None))
+        return ranks, perm
+
+    def sort_ranks_device(self, d_values, d_ranks, d_perm, descending: bool = False,
+                          stream=None) -> None:
+        """Device-resident sort_ranks (bm25_sort_ranks_device): a torch
+        [n_docs] column (int32, int64 or float32) in, int32 [n_docs] ranks and
+        perm out.  A setup call: it allocates the sort's buffers (about 24 bytes
+        per document), synchronises ``stream`` and frees them."""
+        import torch
+        kinds = {torch.int32: 0, torch.float32: 1, torch.int64: 2}
+        if d_values.dtype not in kinds:
+            raise ValueError(f"d_values has dtype {d_values.dtype}: int32, int64 or float32")
+        if tuple(d_values.shape) != (self.n_docs,) or not d_values.is_contiguous():
+            raise ValueError(f"d_values must be a contiguous [{self.n_docs}] tensor (one entry per "
+                             "document)")
+        for name, t in (("d_ranks", d_ranks), ("d_perm", d_perm)):
+            if (t.dtype != torch.int32 or tuple(t.shape) != (self.n_docs,)
+                    or not t.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous int32 [{self.n_docs}] tensor")
+        s = getattr(stream, "cuda_stream", stream) or 0
+        p = lambda t: ctypes.c_void_p(t.data_ptr()) if self.n_docs else None
+        check(lib.bm25_sort_ranks_device(self._h, p(d_values), kinds[d_values.dtype],
+                                         1 if descending else 0, p(d_ranks), p(d_perm),
+                                         ctypes.c_void_p(s)))
+
+    def search_sorted(self, masks, order, k: int, after=None) -> Tuple[np.ndarray, np.ndarray]:
+        """The first k documents of every mask row in a column's order
+        (bm25_search_sorted, host arrays) -> (docs, ranks), int32 [M, k]: row m
+        holds the k allowed documents of smallest rank above its cursor, in
+        rank order, as global doc ids and their ranks; short rows end in
+        padding (doc -1, rank -1).  masks as search_filtered takes them, or an
+        int M: that many rows with every document allowed; order=(ranks, perm)
+        of sort_ranks; after: None or int [M] cursors — a page's last ranks
+        column (-1, a padding slot's rank, gives an all-padding row; -2 is no
+        cursor).  0 <= k <= min(n_docs, 4096)."""
+        if isinstance(masks, (int, np.integer)) and not isinstance(masks, bool):
+            m, M = None, int(masks)
+            if M < 0:
+                raise ValueError("negative mask shape")
+        else:
+            m = self._masks_arg(masks)
+            M = m.shape[0]
+        ranks, perm = _order_arg(order, self.n_docs)
+        k = _sorted_k(k, self.n_docs)
+        a = _after_ranks_arg(after, M)
+        docs = np.zeros((M, k), np.int32)
+        out = np.zeros((M, k), np.int32)
+        check(lib.bm25_search_sorted(self._h, _ptr(m) if m is not None and m.size else None, M,
+                                     _ptr(ranks), _ptr(perm), k, _ptr(a), _ptr(docs), _ptr(out)))
+        return docs, out
+
+    def sorted_scratch_bytes(self, M: int, k: int) -> int:
+        """Bytes of scratch search_sorted_device needs for M rows at k
+        (bm25_search_sorted_scratch)."""
+        v = ctypes.c_int64(0)
+        check(lib.bm25_search_sorted_scratch(self._h, int(M), int(k), ctypes.byref(v)))
+        return int(v.value)
+
+    def search_sorted_device(self, d_masks, d_ranks, d_perm, k: int, d_after, d_docs, d_out_ranks,
+                             d_scratch, stream=None) -> None:
+        """Device-resident search_sorted (bm25_search_sorted_device): packed
+        masks [M, W] (32-bit words; None: every document, M from d_docs), int32
+        [n_docs] ranks and perm, int32 [M] cursors (or None) in, int32 [M, k]
+        docs and ranks out, d_scratch a contiguous byte tensor of at least
+        sorted_scratch_bytes(M, k) (None without masks), enqueued on ``stream``
+        with no host synchronisation and no validation of the order arrays.
+        Reads the caller's tensors only, so it may overlap a search of the
+        same handle."""
+        import torch
+        W = (self.n_docs + 31) // 32
+        k = _sorted_k(k, self.n_docs)
+        if d_docs.dim() != 2 or d_docs.shape[1] != k:
+            raise ValueError(f"d_docs must be an int32 [M, {k}] tensor")
+        M = d_docs.shape[0]
+        if d_masks is not None and (d_masks.dim() != 2 or tuple(d_masks.shape) != (M, W)
+                                    or d_masks.element_size() != 4
+                                    or not d_masks.is_contiguous()):
+            raise ValueError(f"d_masks must be a contiguous packed [{M}, {W}] tensor of 32-bit "
+                             "words")
+        for name, t in (("d_docs", d_docs), ("d_out_ranks", d_out_ranks)):
+            if t.dtype != torch.int32 or tuple(t.shape) != (M, k) or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous int32 [{M}, {k}] tensor")
+        for name, t in (("d_ranks", d_ranks), ("d_perm", d_perm)):
+            if (t.dtype != torch.int32 or tuple(t.shape) != (self.n_docs,)
+                    or not t.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous int32 [{self.n_docs}] tensor")
+        if d_after is not None and (d_after.dtype != torch.int32 or tuple(d_after.shape) != (M,)
+                                    or not d_after.is_contiguous()):
+            raise ValueError(f"d_after must be a contiguous int32 [{M}] tensor (one cursor per row)")
+        nbytes = 0
+        if d_scratch is not None:
+            if not d_scratch.is_contiguous():
+                raise ValueError("d_scratch must be contiguous")
+            nbytes = d_scratch.numel() * d_scratch.element_size()
+        s = getattr(stream, "cuda_stream", stream) or 0
+        p = lambda t, n=1: ctypes.c_void_p(t.data_ptr()) if t is not None and n else None
+        check(lib.bm25_search_sorted_device(
+            self._h, p(d_masks, M and W), M, p(d_ranks), p(d_perm), k, p(d_after, M),
+            p(d_docs, M * k), p(d_out_ranks, M * k), p(d_scratch, nbytes), nbytes,
+            ctypes.c_void_p(s)))
+
     def search_boolean(self, queries: np.ndarray, k: int, must=None, any=None, must_not=None,
                        base=None, *, min_match=None, total_hits: bool = False, facets=None,
-                       ranges=None):
+                       ranges=None, sort=None, after_ranks=None):
         """Top-k of every query among the documents its clause row lets
         through (bm25_search_boolean, host arrays): search_filtered under
         term_masks(must, any, must_not, base) with one mask per query, the
@@ -1221,11 +1417,22 @@ class GpuIndex:
         ranges=(values, fields, lo, hi), as GpuIndex.range_masks takes them
         with one row per query (or (values, lo, hi) for one field), ANDs each
         query's numeric range clauses into its mask, built on the device
-        (bm25_search_boolean_ranges); totals and facets are of that mask."""
+        (bm25_search_boolean_ranges); totals and facets are of that mask.
+        sort=(ranks, perm), as sort_ranks returns them, orders every row by
+        that column instead of by score (bm25_search_boolean_sorted): the
+        first k documents of the query's mask in rank order, their scores
+        score_docs' bits, and the int32 [Q, k] ranks returned after scores
+        (before totals and facets); after_ranks: None or int [Q] cursors, as
+        search_sorted's ``after``.  k <= 4096 then."""
         q = np.ascontiguousarray(queries, dtype=np.int32)
         if q.ndim != 2:
             raise ValueError("queries must be a 2-D [Q, T] int32 array")
         Q, T = q.shape
+        if sort is None and after_ranks is not None:
+            raise ValueError("after_ranks needs sort=(ranks, perm)")
+        if sort is not None:
+            return self._search_boolean_sorted(q, k, must, any, must_not, base, min_match,
+                                               total_hits, facets, ranges, sort, after_ranks)
         mu, an, mn, _, b, Mb = self._clauses_arg(must, any, must_not, base, rows=Q)
         mm = None if min_match is None else min_match_rows(an, min_match, "query")
         if facets is not None:
@@ -1277,6 +1484,48 @@ class GpuIndex:
             mn.shape[1], _ptr(mm), _ptr(b) if Mb else None, Mb, _ptr(docs), _ptr(scores),
             _ptr(totals)))
         return (docs, scores, totals) if total_hits else (docs, scores)
+
+    def _search_boolean_sorted(self, q, k, must, any, must_not, base, min_match, total_hits,
+                               facets, ranges, sort, after_ranks):
+        """search_boolean with sort= (bm25_search_boolean_sorted)."""
+        Q, T = q.shape
+        mu, an, mn, _, b, Mb = self._clauses_arg(must, any, must_not, base, rows=Q)
+        mm = None if min_match is None else min_match_rows(an, min_match, "query")
+        fg, G, give = None, 0, False
+        if facets is not None:
+            if not isinstance(facets, (tuple, list)) or len(facets) != 2:
+                raise ValueError("facets must be a pair (groups, n_groups)")
+            fg, G = _facet_groups(facets[0], facets[1], self.n_docs)
+            give = bool(G and fg.size)
+        ranged = False
+        rv = rf = rlo = rhi = None
+        kind = 0
+        if ranges is not None:
+            rv, kind, rf, rlo, rhi = _range_args(*_ranges_arg(ranges), self.n_docs, rows=Q,
+                                                 what="query")
+            ranged = bool(rv.size and rf.size)
+        ranks, perm = _order_arg(sort, self.n_docs)
+        k = _sorted_k(k, self.n_docs)
+        a = _after_ranks_arg(after_ranks, Q, "query")
+        docs = np.zeros((Q, k), np.int32)
+        scores = np.zeros((Q, k), np.float32)
+        oranks = np.zeros((Q, k), np.int32)
+        totals = np.zeros(Q, np.int64) if total_hits else None
+        counts = np.zeros((Q, G), np.int64) if facets is not None else None
+        check(lib.bm25_search_boolean_sorted(
+            self._h, _ptr(q), Q, T, k, _ptr(mu), mu.shape[1], _ptr(an), an.shape[1], _ptr(mn),
+            mn.shape[1], _ptr(mm), _ptr(b) if Mb else None, Mb, _ptr(fg) if give else None,
+            G if give else 0, _ptr(rv) if ranged else None, kind, rv.shape[0] if ranged else 0,
+            _ptr(rf) if ranged else None, _ptr(rlo) if ranged else None,
+            _ptr(rhi) if ranged else None, rf.shape[1] if ranged else 0, _ptr(docs),
+            _ptr(scores), _ptr(totals), _ptr(counts) if give else None, _ptr(ranks), _ptr(perm),
+            _ptr(a), _ptr(oranks)))
+        out = (docs, scores, oranks)
+        if total_hits:
+            out += (totals,)
+        if facets is not None:
+            out += (counts,)
+        return out
 
     # ------------------------------------------- bm25.BM25's float64 path
     def set_values_f64(self, data64) -> None:

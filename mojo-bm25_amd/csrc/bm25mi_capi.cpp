@@ -1479,6 +1479,26 @@ int check_range_shape(int32_t kind, int64_t F, const void* fields, const void* l
 
 size_t field_bytes(int32_t kind) { return kind == BM25_FIELD_I64 ? 8 : 4; }
 
+int check_kind(int32_t kind) {
+  if (kind != BM25_FIELD_I32 && kind != BM25_FIELD_F32 && kind != BM25_FIELD_I64)
+    return fail(BM25_EINVAL, "kind = %d: BM25_FIELD_I32 (0), BM25_FIELD_F32 (1) or BM25_FIELD_I64 (2)",
+                (int)kind);
+  return BM25_OK;
+}
+
+// The shape of a sorted search: M rows, 0 <= k <= min(n_docs, kMaxK).
+int check_sorted_shape(const bm25_index* h, int64_t M, int32_t k) {
+  if (M < 0) return fail(BM25_EINVAL, "negative mask shape");
+  if (k < 0) return fail(BM25_EINVAL, "negative dimensions are not allowed");
+  if (k > kMaxK)
+    return fail(BM25_EINVAL, "k = %d: a sorted search returns at most %d hits a row", (int)k,
+                (int)kMaxK);
+  if (k > h->ix.n_docs)
+    return fail(BM25_EINVAL, "k = %d is above the index's %lld documents", (int)k,
+                (long long)h->ix.n_docs);
+  return BM25_OK;
+}
+
 // Host range clauses: a field id >= F names no field (a negative one is
 // padding), and a float32 NaN bound would silently match nothing.
 int check_ranges(int32_t kind, int64_t F, const int32_t* fields, const void* lo, const void* hi,
@@ -1549,6 +1569,112 @@ int bm25_range_masks_device(bm25_index* h, const void* d_values, int32_t kind, i
   HIP_TRY(launch_range_masks(h->ix, d_values, kind, F, d_fields, d_lo, d_hi, C, M, d_base, Mb,
                              d_out_masks, (hipStream_t)stream),
           "range_masks launch");
+  return BM25_OK;
+}
+
+int bm25_sort_ranks(bm25_index* h, const void* values, int32_t kind, int32_t descending,
+                    int32_t* out_ranks, int32_t* out_perm) {
+  if (!h) return fail(BM25_EINVAL, "NULL index");
+  const int rc = check_kind(kind);
+  if (rc) return rc;
+  const int64_t n = h->ix.n_docs;
+  if (n == 0) return BM25_OK;
+  if (!values) return fail(BM25_EINVAL, "NULL values");
+  if (!out_ranks || !out_perm) return fail(BM25_EINVAL, "NULL output");
+  Enter in(h);
+  if (in.rc) return in.rc;
+  HostCall c(h->stream);
+  const char* d_values = c.upload((const char*)values, n * (int64_t)field_bytes(kind));
+  int32_t* d_ranks = c.alloc<int32_t>(n);
+  int32_t* d_perm = c.alloc<int32_t>(n);
+  if (c.ok())
+    c.run(launch_sort_ranks(h->ix, d_values, kind, descending != 0, d_ranks, d_perm, h->stream));
+  c.download(out_ranks, d_ranks, n);
+  c.download(out_perm, d_perm, n);
+  return c.finish("sort_ranks");
+}
+
+int bm25_sort_ranks_device(bm25_index* h, const void* d_values, int32_t kind, int32_t descending,
+                           int32_t* d_ranks, int32_t* d_perm, void* stream) {
+  if (!h) return fail(BM25_EINVAL, "NULL index");
+  const int rc = check_kind(kind);
+  if (rc) return rc;
+  if (h->ix.n_docs == 0) return BM25_OK;
+  if (!d_values) return fail(BM25_EINVAL, "NULL values");
+  if (!d_ranks || !d_perm) return fail(BM25_EINVAL, "NULL output");
+  // a setup call: reads the caller's column only, takes and frees the sort's
+  // buffers and waits for `stream` before they go
+  Enter in(h);
+  if (in.rc) return in.rc;
+  HIP_TRY(launch_sort_ranks(h->ix, d_values, kind, descending != 0, d_ranks, d_perm,
+                            (hipStream_t)stream),
+          "sort_ranks");
+  return BM25_OK;
+}
+
+int bm25_search_sorted_scratch(const bm25_index* h, int64_t M, int32_t k, int64_t* bytes) {
+  if (!h || !bytes) return fail(BM25_EINVAL, h ? "NULL output" : "NULL index");
+  const int rc = check_sorted_shape(h, M, k);
+  if (rc) return rc;
+  *bytes = sorted_scratch_bytes(h->ix.n_docs, M, k);
+  return BM25_OK;
+}
+
+int bm25_search_sorted(bm25_index* h, const uint32_t* masks, int64_t M, const int32_t* ranks,
+                       const int32_t* perm, int32_t k, const int32_t* after_ranks,
+                       int32_t* out_docs, int32_t* out_ranks) {
+  if (!h) return fail(BM25_EINVAL, "NULL index");
+  int rc = check_sorted_shape(h, M, k);
+  if (rc) return rc;
+  if (M == 0 || k == 0) return BM25_OK;
+  if (!ranks || !perm) return fail(BM25_EINVAL, "NULL ranks or perm");
+  if (!out_docs || !out_ranks) return fail(BM25_EINVAL, "NULL output");
+  const int64_t n = h->ix.n_docs, W = (n + 31) >> 5;
+  rc = check_sort_order(ranks, perm, n);
+  if (rc) return rc;
+  rc = check_after_ranks(after_ranks, M);
+  if (rc) return rc;
+  Enter in(h);
+  if (in.rc) return in.rc;
+  // staging buffers of this call's own (as bm25_mask_facets)
+  HostCall c(h->stream);
+  const uint32_t* d_masks = c.upload(masks, masks ? M * W : 0);
+  const int32_t* d_ranks = c.upload(ranks, n);
+  const int32_t* d_perm = c.upload(perm, n);
+  const int32_t* d_after = c.upload(after_ranks, after_ranks ? M : 0);
+  int32_t* d_docs = c.alloc<int32_t>(M * k);
+  int32_t* d_or = c.alloc<int32_t>(M * k);
+  char* d_scratch = c.alloc<char>(sorted_scratch_bytes(n, M, k));
+  if (c.ok())
+    c.run(launch_search_sorted(h->ix, d_masks, M, d_ranks, d_perm, k, d_after, d_docs, d_or,
+                               d_scratch, h->ix.opt.sorted_bins, h->stream));
+  c.download(out_docs, d_docs, M * k);
+  c.download(out_ranks, d_or, M * k);
+  return c.finish("search_sorted");
+}
+
+int bm25_search_sorted_device(bm25_index* h, const uint32_t* d_masks, int64_t M,
+                              const int32_t* d_ranks, const int32_t* d_perm, int32_t k,
+                              const int32_t* d_after_ranks, int32_t* d_docs, int32_t* d_out_ranks,
+                              void* d_scratch, int64_t scratch_bytes, void* stream) {
+  if (!h) return fail(BM25_EINVAL, "NULL index");
+  const int rc = check_sorted_shape(h, M, k);
+  if (rc) return rc;
+  if (M == 0 || k == 0) return BM25_OK;
+  if (!d_ranks || !d_perm) return fail(BM25_EINVAL, "NULL ranks or perm");
+  if (!d_docs || !d_out_ranks) return fail(BM25_EINVAL, "NULL output");
+  const int64_t need = sorted_scratch_bytes(h->ix.n_docs, M, k);
+  if (d_masks && (!d_scratch || scratch_bytes < need))
+    return fail(BM25_EINVAL, "scratch of %lld bytes: bm25_search_sorted_scratch asks for %lld",
+                (long long)(d_scratch ? scratch_bytes : 0), (long long)need);
+  if (((uintptr_t)d_scratch & 3u) != 0) return fail(BM25_EINVAL, "scratch must be 4-byte aligned");
+  // reads the caller's buffers only (as bm25_mask_facets_device: no workspace,
+  // no index array, no ordering against the handle's searches)
+  Enter in(h);
+  if (in.rc) return in.rc;
+  HIP_TRY(launch_search_sorted(h->ix, d_masks, M, d_ranks, d_perm, k, d_after_ranks, d_docs,
+                               d_out_ranks, d_scratch, h->ix.opt.sorted_bins, (hipStream_t)stream),
+          "search_sorted launch");
   return BM25_OK;
 }
 
@@ -1727,7 +1853,25 @@ int bm25_search_boolean_ranges(bm25_index* h, const int32_t* queries, int64_t Q,
                                int64_t F, const int32_t* fields, const void* lo, const void* hi,
                                int64_t C, int32_t* out_docs, float* out_scores,
                                int64_t* out_total_hits, int64_t* out_facets) {
+  return bm25_search_boolean_sorted(h, queries, Q, T, k, must, A, any, B, must_not, N, min_match,
+                                    base, Mb, groups, G, values, kind, F, fields, lo, hi, C,
+                                    out_docs, out_scores, out_total_hits, out_facets, nullptr,
+                                    nullptr, nullptr, nullptr);
+}
+
+int bm25_search_boolean_sorted(bm25_index* h, const int32_t* queries, int64_t Q, int64_t T,
+                               int32_t k, const int32_t* must, int64_t A, const int32_t* any,
+                               int64_t B, const int32_t* must_not, int64_t N,
+                               const int32_t* min_match, const uint32_t* base, int64_t Mb,
+                               const int32_t* groups, int64_t G, const void* values, int32_t kind,
+                               int64_t F, const int32_t* fields, const void* lo, const void* hi,
+                               int64_t C, int32_t* out_docs, float* out_scores,
+                               int64_t* out_total_hits, int64_t* out_facets, const int32_t* ranks,
+                               const int32_t* perm, const int32_t* after_ranks,
+                               int32_t* out_ranks) {
   if (!h) return fail(BM25_EINVAL, "NULL index");
+  // (ranks == NULL: bm25_search_boolean_ranges, the order by score)
+  const bool sorted = ranks != nullptr;
   if (Q < 0 || T < 0) return fail(BM25_EINVAL, "negative query shape");
   int rc = check_clauses(must, A, any, B, must_not, N, Q, base, Mb);
   if (rc) return rc;
@@ -1747,11 +1891,22 @@ int bm25_search_boolean_ranges(bm25_index* h, const int32_t* queries, int64_t Q,
   if (G == 0 || !groups) out_facets = nullptr;  // (no group: no facet row to write)
   rc = check_k(h, k);
   if (rc) return rc;
+  if (sorted && k > kMaxK)
+    return fail(BM25_EINVAL, "k = %d: a sorted search returns at most %d hits a row", (int)k,
+                (int)kMaxK);
   // (k == 0 with out_total_hits or out_facets: "how many match" alone — the
   // masks are still built and counted)
   if (Q == 0 || (k == 0 && !out_total_hits && !out_facets)) return BM25_OK;
   if (k > 0 && T > 0 && !queries) return fail(BM25_EINVAL, "NULL queries");
   if (k > 0 && (!out_docs || !out_scores)) return fail(BM25_EINVAL, "NULL output");
+  if (sorted && k > 0) {
+    if (!perm) return fail(BM25_EINVAL, "NULL perm");
+    if (!out_ranks) return fail(BM25_EINVAL, "NULL output");
+    rc = check_sort_order(ranks, perm, h->ix.n_docs);
+    if (rc) return rc;
+    rc = check_after_ranks(after_ranks, Q);
+    if (rc) return rc;
+  }
   rc = check_clause_ids(h, max_token(0, queries, k > 0 ? Q * T : 0), must, A, any, B, must_not, N,
                         Q);
   if (rc) return rc;
@@ -1805,6 +1960,15 @@ int bm25_search_boolean_ranges(bm25_index* h, const int32_t* queries, int64_t Q,
   int32_t* d_qm = c.alloc<int32_t>(chunk);
   c.upload_to(d_qm, ids.data(), chunk);
   if (k > 0) c.upload_to(h->d_q, queries, Q * T);
+  // the order goes up once per call; a chunk's rows are selected by rank into
+  // the staging rows, in scratch of this call's own
+  const bool by_rank = sorted && k > 0;
+  const int32_t* d_ranks = by_rank ? c.upload(ranks, h->ix.n_docs) : nullptr;
+  const int32_t* d_perm = by_rank ? c.upload(perm, h->ix.n_docs) : nullptr;
+  const int32_t* d_after = by_rank && after_ranks ? c.upload(after_ranks, Q) : nullptr;
+  int32_t* d_oranks = by_rank ? c.alloc<int32_t>(Q * k) : nullptr;
+  char* d_sscratch =
+      by_rank ? c.alloc<char>(sorted_scratch_bytes(h->ix.n_docs, chunk, k)) : nullptr;
   int64_t n_dense = 0;
   for (int64_t q0 = 0; c.ok() && q0 < Q; q0 += chunk) {
     const int64_t n = std::min(chunk, Q - q0);
@@ -1825,13 +1989,27 @@ int bm25_search_boolean_ranges(bm25_index* h, const int32_t* queries, int64_t Q,
       c.run(launch_mask_facets(h->ix, d_masks, n, d_groups, G, d_facets + q0 * G, h->stream));
     if (!c.ok()) break;
     if (k == 0) continue;  // (the counts alone: no search ran, the handle's counters stay)
+    if (by_rank) {
+      // the rows by rank, their scores by the point lookup (a padding slot
+      // scores +0.0f there), then the tails' score bits
+      c.run(launch_search_sorted(h->ix, d_masks, n, d_ranks, d_perm, k,
+                                 d_after ? d_after + q0 : nullptr, h->d_docs + q0 * k,
+                                 d_oranks + q0 * k, d_sscratch, h->ix.opt.sorted_bins, h->stream));
+      if (c.ok())
+        c.run(launch_score_docs(h->ix, h->d_q + q0 * T, n, T, h->d_docs + q0 * k, k,
+                                h->d_scores + q0 * k, h->stream));
+      if (c.ok())
+        c.run(launch_sorted_pad_scores(h->d_docs + q0 * k, h->d_scores + q0 * k, n * k, h->stream));
+      continue;
+    }
     c.hold(run_filtered(h, h->d_q + q0 * T, n, T, k, d_masks, n, d_qm, h->d_docs + q0 * k,
                         h->d_scores + q0 * k, h->stream));
     n_dense += h->filtered_dense;
   }
-  if (k > 0) h->filtered_dense = n_dense;
+  if (k > 0 && !by_rank) h->filtered_dense = n_dense;
   c.download(out_docs, h->d_docs, Q * k);
   c.download(out_scores, h->d_scores, Q * k);
+  if (by_rank) c.download(out_ranks, d_oranks, Q * k);
   if (d_hits) c.download(out_total_hits, d_hits, Q);
   if (d_facets) c.download(out_facets, d_facets, Q * G);
   return c.finish("boolean search");

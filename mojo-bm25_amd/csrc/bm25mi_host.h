@@ -145,7 +145,36 @@ inline constexpr OptDesc kOptsMore[] = {
      nullptr},
     {"collapse_chunk", "BM25_COLLAPSE_CHUNK", &SearchOpts::collapse_chunk, kOptRange, 0, 1 << 30, 1,
      "collapse_chunk must be in 0..2^30"},
+    {"sorted_bins", "BM25_SORTED_BINS", &SearchOpts::sorted_bins, kOptRange, 0, (int)kSortedBins, 2,
+     nullptr},
 };
+
+// The order arrays and cursors of the sorted search as the host calls check
+// them (bm25_search_sorted, bm25_search_boolean_sorted): ranks and perm inverse
+// permutations of [0, n_docs) — the message names the first offending index —
+// and no cursor below BM25_AFTER_NONE.
+// (inline, so tests/asan/sorted_check.cpp drives them under the sanitizers with
+// a fail() of its own and no device)
+inline int check_sort_order(const int32_t* ranks, const int32_t* perm, int64_t n_docs) {
+  for (int64_t d = 0; d < n_docs; ++d) {  // (perm[ranks[d]] == d for every d shows both)
+    const int32_t r = ranks[d];
+    if (r < 0 || r >= n_docs)
+      return fail(BM25_EINVAL, "ranks[%lld] = %d is outside [0, %lld)", (long long)d, (int)r,
+                  (long long)n_docs);
+    if (perm[r] != d)
+      return fail(BM25_EINVAL,
+                  "ranks[%lld] = %d but perm[%d] = %d: ranks and perm are not inverse permutations",
+                  (long long)d, (int)r, (int)r, (int)perm[r]);
+  }
+  return BM25_OK;
+}
+inline int check_after_ranks(const int32_t* after, int64_t M) {
+  for (int64_t m = 0; after && m < M; ++m)
+    if (after[m] < BM25_AFTER_NONE)
+      return fail(BM25_EINVAL, "after_ranks[%lld] = %d is below BM25_AFTER_NONE (-2)", (long long)m,
+                  (int)after[m]);
+  return BM25_OK;
+}
 
 // Sets / reads one option by name (EINVAL names the accepted values).
 int set_opt(SearchOpts& o, const char* name, int64_t v);

@@ -103,6 +103,7 @@ struct SearchOpts {
                            // [1, min(n_docs, kMaxK)])
   int collapse_chunk = 0;  // ... rows per sub-batch of the rounds under exclusion masks (0: auto,
                            // <= 1 GiB of mask words)
+  int sorted_bins = 0;     // sorted search: histogram bins per level (0 or 1: auto, kSortedBins)
 };
 
 // What the last search launched (bm25_search_dispatch).
@@ -620,6 +621,52 @@ hipError_t launch_range_masks(const DevIndex& ix, const void* d_values, int kind
                               const int32_t* d_fields, const void* d_lo, const void* d_hi,
                               int64_t C, int64_t M, const uint32_t* d_base, int64_t Mb,
                               uint32_t* d_out, hipStream_t stream);
+
+// Sort-by-field search (bm25mi_sorted.hip; bm25_sort_ranks / bm25_search_sorted,
+// include/bm25mi.h).
+//   launch_sort_ranks: the order of the n_docs documents by (d_values' column
+//     order, doc id ascending) as d_perm[r] = the document at rank r and
+//     d_ranks[d] = the rank of document d (kind: kField*; descending reverses
+//     the numbers only, NaN stays last).  A setup call: it allocates the sort's
+//     buffers (24 B per document, two (u64 key, u32 value) arrays, plus
+//     radix_sort_scratch_bytes), synchronises `stream` and frees them.
+//   launch_search_sorted: row m of d_docs / d_out_ranks [M][k] = the k documents
+//     of smallest rank among those d_masks[m][W] allows (null: every document)
+//     with d_ranks[d] > d_after[m] (null or < -1: no cursor; -1: an all-padding
+//     row), as (d_perm[rank] + doc_offset, rank), padded with -1 / -1.  Reads no
+//     mask word at index >= W of a row, ignores bits at or past n_docs, treats a
+//     rank outside [0, n_docs) as never eligible, and writes nothing outside
+//     the outputs and d_scratch (sorted_scratch_bytes(n_docs, M, k) bytes, 4-byte
+//     aligned) whatever d_ranks and d_perm hold.  Integer only; the global
+//     atomics are integer adds.  0 < k <= min(n_docs, kMaxK).  bins: histogram
+//     bins per level (< 2: kSortedBins; at most kSortedBins).
+//   launch_sorted_pad_scores: d_scores[i] = bits 0xFFFFFFFF where d_docs[i] < 0.
+// Selection geometry: a workgroup takes a slice of documents and a block of
+// kSortedRows mask rows; each of its waves walks spans of kSortedSpanDocs
+// documents in steps of 64; a row's rank interval is narrowed level by level
+// until it is at most kSortedWmax ranks wide, then collected and sorted in LDS.
+constexpr int64_t kSortedRows = 32;        // mask rows of a row block (LDS bins per row)
+constexpr int64_t kSortedSpanDocs = 256;   // documents of a wave's span (8 words per lane)
+constexpr int64_t kSortedRoundDocs = 1024; // documents of a workgroup's round (4 spans)
+constexpr int64_t kSortedBins = 256;       // histogram bins per level, at most (and automatic)
+constexpr int64_t kSortedWmax = 2048;      // a row's interval is collected at this width
+constexpr int64_t kSortedSortP = 8192;     // keys the row sort holds in LDS
+static_assert(kMaxK + kSortedWmax <= kSortedSortP, "a row's list fits the LDS sort");
+inline int64_t sorted_list_cap(int64_t n_docs, int64_t k) {
+  return std::min<int64_t>(k + kSortedWmax, n_docs);
+}
+// bytes = 4 M (4 state + 1 count + kSortedBins histogram + sorted_list_cap list)
+inline int64_t sorted_scratch_bytes(int64_t n_docs, int64_t M, int64_t k) {
+  return 4 * M * (4 + 1 + kSortedBins + sorted_list_cap(n_docs, k));
+}
+hipError_t launch_sort_ranks(const DevIndex& ix, const void* d_values, int kind, bool descending,
+                             int32_t* d_ranks, int32_t* d_perm, hipStream_t stream);
+hipError_t launch_search_sorted(const DevIndex& ix, const uint32_t* d_masks, int64_t M,
+                                const int32_t* d_ranks, const int32_t* d_perm, int32_t k,
+                                const int32_t* d_after, int32_t* d_docs, int32_t* d_out_ranks,
+                                void* d_scratch, int bins, hipStream_t stream);
+hipError_t launch_sorted_pad_scores(const int32_t* d_docs, float* d_scores, int64_t n,
+                                    hipStream_t stream);
 
 // Field collapsing (bm25mi_collapse.hip; the loop is run_collapsed of
 // bm25mi_capi.cpp).  State by row q of the call: d_count[q] hits kept so far
