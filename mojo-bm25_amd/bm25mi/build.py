@@ -107,24 +107,30 @@ def build_asan_check(verbose: bool = False) -> str:
     return exe
 
 
-def build_sorted_check(verbose: bool = False) -> str:
-    """tests/asan/sorted_check built by the host compiler alone with
-    AddressSanitizer and UBSan (-fsanitize=address,undefined; it includes the
-    host headers, makes no HIP call and links none), into
-    mojo-bm25_amd/bm25mi/_asan/ (rebuilt when a source is newer).  Test
-    infrastructure for tests/test_search_sorted_host.py, not the product."""
+def build_host_program(name: str, verbose: bool = False) -> str:
+    """tests/asan/<name>.cpp (sorted_check, ranked_check) built by the host
+    compiler alone with AddressSanitizer and UBSan
+    (-fsanitize=address,undefined; it includes the host headers, makes no HIP
+    call and links none), into mojo-bm25_amd/bm25mi/_asan/ (rebuilt when a
+    source is newer).  Test infrastructure for tests/test_search_sorted_host.py
+    and tests/test_ranked_args_host.py, not the product."""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     rocm_inc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(hipcc))), "include")
     out = os.path.join(PKG_DIR, "_asan")
     os.makedirs(out, exist_ok=True)
-    exe = os.path.join(out, "sorted_check")
-    main = os.path.join(REPO, "tests", "asan", "sorted_check.cpp")
+    exe = os.path.join(out, name)
+    main = os.path.join(REPO, "tests", "asan", name + ".cpp")
     if _stale(exe, [main] + HEADERS):
         _run(["g++", "-std=c++17", "-O1", "-g", "-w", "-fsanitize=address,undefined",
               "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-D__HIP_PLATFORM_AMD__",
               "-I", rocm_inc, "-o", exe + ".tmp", main], verbose)
         os.replace(exe + ".tmp", exe)
     return exe
+
+
+def build_sorted_check(verbose: bool = False) -> str:
+    """build_host_program("sorted_check")."""
+    return build_host_program("sorted_check", verbose)
 
 
 if __name__ == "__main__":

@@ -19,6 +19,21 @@ def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
+def _dptr(t):
+    """The device pointer of a torch tensor (None: NULL)."""
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _stream(stream) -> int:
+    """A torch stream, a raw stream handle or None (the null stream) -> the handle."""
+    return getattr(stream, "cuda_stream", stream) or 0
+
+
+def _topk_out(Q: int, k: int) -> Tuple[np.ndarray, np.ndarray]:
+    """The (docs, scores) arrays a host search fills (k < 0: the C call's error)."""
+    return np.zeros((Q, max(k, 0)), np.int32), np.zeros((Q, max(k, 0)), np.float32)
+
+
 def pack_mask(allow) -> np.ndarray:
     """Allow-masks for the filtered search: bool [n_docs] or [M, n_docs] ->
     uint32 [M, W], W = ceil(n_docs / 32), document d at bit d & 31 of word
@@ -448,15 +463,14 @@ class GpuIndex:
             raise ValueError("queries must be a 2-D [Q, T] int32 array")
         Q, T = q.shape
         k = int(k)
-        docs = np.zeros((Q, max(k, 0)), np.int32)
-        scores = np.zeros((Q, max(k, 0)), np.float32)
+        docs, scores = _topk_out(Q, k)
         check(lib.bm25_search(self._h, _ptr(q), Q, T, k, _ptr(docs), _ptr(scores)))
         return docs, scores
 
     def max_token_device(self, d_queries, stream=None) -> int:
         """Largest token id of a device batch (bm25_max_token_device; syncs)."""
         Q, T = d_queries.shape
-        s = getattr(stream, "cuda_stream", stream) or 0
+        s = _stream(stream)
         m = ctypes.c_int32()
         check(lib.bm25_max_token_device(self._h, ctypes.c_void_p(d_queries.data_ptr()), Q, T,
                                         ctypes.byref(m), ctypes.c_void_p(s)))
@@ -469,7 +483,7 @@ class GpuIndex:
         >= n_terms count as padding unless ``validate`` (a synchronising
         device check) raises the reference's ValueError (bm25_native.py:91-96)."""
         Q, T = d_queries.shape
-        s = getattr(stream, "cuda_stream", stream) or 0
+        s = _stream(stream)
         if validate:
             m = self.max_token_device(d_queries, stream)
             if m >= self.n_terms:
@@ -491,7 +505,7 @@ class GpuIndex:
                              stream=None) -> None:
         """This shard's sample keys (torch int64/uint64 [Q, S] on the device)."""
         Q, T = d_queries.shape
-        s = getattr(stream, "cuda_stream", stream) or 0
+        s = _stream(stream)
         check(lib.bm25_search_sample_device(self._h, ctypes.c_void_p(d_queries.data_ptr()), Q, T,
                                             int(k), int(world), int(shard_docs_max),
                                             ctypes.c_void_p(d_keys.data_ptr()),
@@ -502,7 +516,7 @@ class GpuIndex:
         """Global theta from every shard's sample keys ([W, Q, S]), then this
         shard's keys >= theta as a padded [Q, k] list (global doc ids)."""
         Q, T = d_queries.shape
-        s = getattr(stream, "cuda_stream", stream) or 0
+        s = _stream(stream)
         check(lib.bm25_search_finish_device(self._h, ctypes.c_void_p(d_queries.data_ptr()), Q, T,
                                             int(k), int(world), int(shard_docs_max),
                                             ctypes.c_void_p(d_all_keys.data_ptr()),
@@ -516,7 +530,7 @@ class GpuIndex:
         """search_finish_device on three streams (bm25_search_finish_streams_
         device): theta, the REST pass and the merges, ordered by events."""
         Q, T = d_queries.shape
-        ss = [getattr(x, "cuda_stream", x) or 0 for x in (stream_theta, stream_rest, stream_select)]
+        ss = [_stream(x) for x in (stream_theta, stream_rest, stream_select)]
         check(lib.bm25_search_finish_streams_device(
             self._h, ctypes.c_void_p(d_queries.data_ptr()), Q, T, int(k), int(world),
             int(shard_docs_max), ctypes.c_void_p(d_all_keys.data_ptr()),
@@ -531,7 +545,7 @@ class GpuIndex:
     def bounds_export(self, d_out, stride: int, stream=None) -> None:
         """This index's tile bounds into d_out (a torch int16 [n_terms, stride]
         device tensor; bm25_index_bounds_export)."""
-        s = getattr(stream, "cuda_stream", stream) or 0
+        s = _stream(stream)
         check(lib.bm25_index_bounds_export(self._h, ctypes.c_void_p(d_out.data_ptr()), int(stride),
                                            ctypes.c_void_p(s)))
 
@@ -540,7 +554,7 @@ class GpuIndex:
         [n_terms, stride] device tensor, stride as bounds_stride();
         bm25_index_masks_export).  Bit s of (term, tile): the term has a
         posting in the tile's s-th sub-block of tile_docs / 32 documents."""
-        s = getattr(stream, "cuda_stream", stream) or 0
+        s = _stream(stream)
         check(lib.bm25_index_masks_export(self._h, ctypes.c_void_p(d_out.data_ptr()), int(stride),
                                           ctypes.c_void_p(s)))
 
@@ -561,7 +575,7 @@ class GpuIndex:
         """This shard's keys >= the collection's threshold (world bounds) as an
         unsorted padded [Q, k] list for the W-way merge (bm25_search_shard_device)."""
         Q, T = d_queries.shape
-        s = getattr(stream, "cuda_stream", stream) or 0
+        s = _stream(stream)
         check(lib.bm25_search_shard_device(self._h, ctypes.c_void_p(d_queries.data_ptr()), Q, T,
                                            int(k), ctypes.c_void_p(d_docs.data_ptr()),
                                            ctypes.c_void_p(d_scores.data_ptr()),
@@ -608,7 +622,7 @@ class GpuIndex:
         C = d_docs.shape[1]
         if d_scores.numel() != Q * C:
             raise ValueError(f"d_scores must hold {Q} x {C} scores")
-        s = getattr(stream, "cuda_stream", stream) or 0
+        s = _stream(stream)
         check(lib.bm25_score_docs_device(self._h, ctypes.c_void_p(d_queries.data_ptr()), Q, T,
                                          ctypes.c_void_p(d_docs.data_ptr()), C,
                                          ctypes.c_void_p(d_scores.data_ptr()), ctypes.c_void_p(s)))
@@ -634,20 +648,21 @@ class GpuIndex:
                              f"got shape {m.shape}")
         return np.ascontiguousarray(m)
 
-    def search_filtered(self, queries: np.ndarray, k: int, masks,
-                        query_mask=None) -> Tuple[np.ndarray, np.ndarray]:
-        """Top-k of every query among the documents its mask allows
-        (bm25_search_filtered, host arrays).  queries int32 [Q, T]; masks bool
-        [M, n_docs] (or [n_docs]) or packed uint32 [M, W] (pack_mask), bits by
-        this handle's own documents; query_mask int32 [Q] picks each query's
-        mask (-1: no filter; None: mask 0 for every query).  Rows with fewer
-        than k allowed documents end in padding (doc -1, score bits ~0)."""
+    def _ranked_args(self, queries, weights, masks, query_mask, need_weights=False,
+                     need_masks=False):
+        """The host arrays of a ranked search -> (q, w, m, M, qm): int32 [Q, T]
+        queries, float32 weights or None, packed masks [M, W] or None, int32
+        [Q] mask ids in [-1, M) or None (shape errors raised here, before any C
+        call).  need_weights: weights are no option (search_weighted);
+        need_masks: nor are the masks, and without a mask row the mask ids are
+        none either (search_filtered)."""
         q = np.ascontiguousarray(queries, dtype=np.int32)
         if q.ndim != 2:
             raise ValueError("queries must be a 2-D [Q, T] int32 array")
-        Q, T = q.shape
-        m = self._masks_arg(masks)
-        M = m.shape[0]
+        Q = q.shape[0]
+        w = self._weights_arg(q, weights) if need_weights or weights is not None else None
+        m = self._masks_arg(masks) if need_masks or masks is not None else None
+        M = 0 if m is None else m.shape[0]
         qm = None
         if query_mask is not None:
             qm = np.ascontiguousarray(query_mask, dtype=np.int32)
@@ -656,11 +671,50 @@ class GpuIndex:
                                  f"got shape {qm.shape}")
             if qm.size and (int(qm.min()) < -1 or int(qm.max()) >= M):
                 raise ValueError(f"query_mask entries must be in [-1, {M})")
-        elif M == 0 and Q > 0:
+        elif need_masks and M == 0 and Q > 0:
             raise ValueError("no masks given: query_mask must be -1 for every query")
+        return q, w, m, M, qm
+
+    def _ranked_device_args(self, d_queries, d_weights, d_masks, d_query_mask, need_weights=False,
+                            need_masks=False) -> Tuple[int, int, int]:
+        """The shapes of a device-resident ranked search's tensors -> (Q, T, M);
+        need_weights / need_masks as in _ranked_args."""
+        if d_queries.dim() != 2:
+            raise ValueError("d_queries must be a 2-D [Q, T] tensor")
+        Q, T = d_queries.shape
+        if (need_weights or d_weights is not None) and (
+                tuple(d_weights.shape) != (Q, T) or not d_weights.dtype.is_floating_point
+                or d_weights.element_size() != 4):
+            raise ValueError(f"d_weights must be a float32 [{Q}, {T}] tensor")
+        W = (self.n_docs + 31) // 32
+        M = 0
+        if need_masks or d_masks is not None:
+            if d_masks.dim() != 2 or d_masks.shape[1] != W or d_masks.element_size() != 4:
+                raise ValueError(f"d_masks must be a packed [M, {W}] tensor of 32-bit words")
+            M = d_masks.shape[0]
+        if d_query_mask is not None and d_query_mask.numel() != Q:
+            raise ValueError(f"d_query_mask must hold one mask id per query ({Q})")
+        if need_masks and d_query_mask is None and M == 0 and Q > 0:
+            raise ValueError("no masks given: d_query_mask must be -1 for every query")
+        return Q, T, M
+
+    @staticmethod
+    def _device_out(d_docs, d_scores, Q: int, k: int) -> None:
+        if d_docs.numel() != Q * k or d_scores.numel() != Q * k:
+            raise ValueError(f"d_docs and d_scores must hold {Q} x {k} results")
+
+    def search_filtered(self, queries: np.ndarray, k: int, masks,
+                        query_mask=None) -> Tuple[np.ndarray, np.ndarray]:
+        """Top-k of every query among the documents its mask allows
+        (bm25_search_filtered, host arrays).  queries int32 [Q, T]; masks bool
+        [M, n_docs] (or [n_docs]) or packed uint32 [M, W] (pack_mask), bits by
+        this handle's own documents; query_mask int32 [Q] picks each query's
+        mask (-1: no filter; None: mask 0 for every query).  Rows with fewer
+        than k allowed documents end in padding (doc -1, score bits ~0)."""
+        q, _, m, M, qm = self._ranked_args(queries, None, masks, query_mask, need_masks=True)
+        Q, T = q.shape
         k = int(k)
-        docs = np.zeros((Q, max(k, 0)), np.int32)
-        scores = np.zeros((Q, max(k, 0)), np.float32)
+        docs, scores = _topk_out(Q, k)
         check(lib.bm25_search_filtered(self._h, _ptr(q), Q, T, k, _ptr(m) if M else None, M,
                                        _ptr(qm), _ptr(docs), _ptr(scores)))
         return docs, scores
@@ -674,27 +728,13 @@ class GpuIndex:
         n_terms are padding and the mask ids must be in [-1, M).  It may
         synchronise ``stream`` once, to count the queries whose candidate list
         overflowed (they take the dense path)."""
-        if d_queries.dim() != 2:
-            raise ValueError("d_queries must be a 2-D [Q, T] tensor")
-        Q, T = d_queries.shape
-        W = (self.n_docs + 31) // 32
-        if d_masks.dim() != 2 or d_masks.shape[1] != W or d_masks.element_size() != 4:
-            raise ValueError(f"d_masks must be a packed [M, {W}] tensor of 32-bit words")
-        M = d_masks.shape[0]
-        if d_query_mask is not None and d_query_mask.numel() != Q:
-            raise ValueError(f"d_query_mask must hold one mask id per query ({Q})")
-        if d_query_mask is None and M == 0 and Q > 0:
-            raise ValueError("no masks given: d_query_mask must be -1 for every query")
+        Q, T, M = self._ranked_device_args(d_queries, None, d_masks, d_query_mask,
+                                           need_masks=True)
         k = int(k)
-        if d_docs.numel() != Q * k or d_scores.numel() != Q * k:
-            raise ValueError(f"d_docs and d_scores must hold {Q} x {k} results")
-        s = getattr(stream, "cuda_stream", stream) or 0
-        qm = None if d_query_mask is None else ctypes.c_void_p(d_query_mask.data_ptr())
+        self._device_out(d_docs, d_scores, Q, k)
         check(lib.bm25_search_filtered_device(
-            self._h, ctypes.c_void_p(d_queries.data_ptr()), Q, T, k,
-            ctypes.c_void_p(d_masks.data_ptr()) if M else None, M, qm,
-            ctypes.c_void_p(d_docs.data_ptr()), ctypes.c_void_p(d_scores.data_ptr()),
-            ctypes.c_void_p(s)))
+            self._h, _dptr(d_queries), Q, T, k, _dptr(d_masks) if M else None, M,
+            _dptr(d_query_mask), _dptr(d_docs), _dptr(d_scores), ctypes.c_void_p(_stream(stream))))
 
     def filtered_stats(self) -> Tuple[int, int, int]:
         """Counters of the last filtered search (bm25_search_filtered_stats):
@@ -725,24 +765,10 @@ class GpuIndex:
         padding; the weight of a padding slot is ignored, every other must be
         finite.  masks / query_mask as in search_filtered; masks None: no
         filter (query_mask must then be None or all -1)."""
-        q = np.ascontiguousarray(queries, dtype=np.int32)
-        if q.ndim != 2:
-            raise ValueError("queries must be a 2-D [Q, T] int32 array")
+        q, w, m, M, qm = self._ranked_args(queries, weights, masks, query_mask, need_weights=True)
         Q, T = q.shape
-        w = self._weights_arg(q, weights)
-        m = None if masks is None else self._masks_arg(masks)
-        M = 0 if m is None else m.shape[0]
-        qm = None
-        if query_mask is not None:
-            qm = np.ascontiguousarray(query_mask, dtype=np.int32)
-            if qm.ndim != 1 or qm.size != Q:
-                raise ValueError(f"query_mask must hold one mask id per query ({Q}), "
-                                 f"got shape {qm.shape}")
-            if qm.size and (int(qm.min()) < -1 or int(qm.max()) >= M):
-                raise ValueError(f"query_mask entries must be in [-1, {M})")
         k = int(k)
-        docs = np.zeros((Q, max(k, 0)), np.int32)
-        scores = np.zeros((Q, max(k, 0)), np.float32)
+        docs, scores = _topk_out(Q, k)
         check(lib.bm25_search_weighted(self._h, _ptr(q), _ptr(w), Q, T, k, _ptr(m) if M else None,
                                        M, _ptr(qm), _ptr(docs), _ptr(scores)))
         return docs, scores
@@ -757,32 +783,39 @@ class GpuIndex:
         padding, the weights of non-padding slots must be finite and the mask
         ids in [-1, M).  It may synchronise ``stream`` once, as
         search_filtered_device."""
-        if d_queries.dim() != 2:
-            raise ValueError("d_queries must be a 2-D [Q, T] tensor")
-        Q, T = d_queries.shape
-        if (tuple(d_weights.shape) != (Q, T) or not d_weights.dtype.is_floating_point
-                or d_weights.element_size() != 4):
-            raise ValueError(f"d_weights must be a float32 [{Q}, {T}] tensor")
-        W = (self.n_docs + 31) // 32
-        M = 0
-        if d_masks is not None:
-            if d_masks.dim() != 2 or d_masks.shape[1] != W or d_masks.element_size() != 4:
-                raise ValueError(f"d_masks must be a packed [M, {W}] tensor of 32-bit words")
-            M = d_masks.shape[0]
-        if d_query_mask is not None and d_query_mask.numel() != Q:
-            raise ValueError(f"d_query_mask must hold one mask id per query ({Q})")
+        Q, T, M = self._ranked_device_args(d_queries, d_weights, d_masks, d_query_mask,
+                                           need_weights=True)
         k = int(k)
-        if d_docs.numel() != Q * k or d_scores.numel() != Q * k:
-            raise ValueError(f"d_docs and d_scores must hold {Q} x {k} results")
-        s = getattr(stream, "cuda_stream", stream) or 0
-        qm = None if d_query_mask is None else ctypes.c_void_p(d_query_mask.data_ptr())
+        self._device_out(d_docs, d_scores, Q, k)
         check(lib.bm25_search_weighted_device(
-            self._h, ctypes.c_void_p(d_queries.data_ptr()), ctypes.c_void_p(d_weights.data_ptr()),
-            Q, T, k, ctypes.c_void_p(d_masks.data_ptr()) if M else None, M, qm,
-            ctypes.c_void_p(d_docs.data_ptr()), ctypes.c_void_p(d_scores.data_ptr()),
-            ctypes.c_void_p(s)))
+            self._h, _dptr(d_queries), _dptr(d_weights), Q, T, k, _dptr(d_masks) if M else None,
+            M, _dptr(d_query_mask), _dptr(d_docs), _dptr(d_scores),
+            ctypes.c_void_p(_stream(stream))))
 
     # ---------------------------------------------------- cursor pagination
+    @staticmethod
+    def _after_arg(after, Q: int):
+        """The ``after`` of search_after -> (float32 [Q] scores, int32 [Q] docs),
+        or (None, None): no cursor."""
+        if after is None:
+            return None, None
+        if not isinstance(after, (tuple, list)) or len(after) != 2:
+            raise ValueError("after must be None or a pair (scores [Q], docs [Q])")
+        if after[0] is None or after[1] is None:
+            raise ValueError("after needs both halves: (scores [Q], docs [Q])")
+        a_s, a_d = np.asarray(after[0]), np.asarray(after[1])
+        if a_s.dtype != np.float32 or a_d.dtype != np.int32:
+            raise ValueError("after must be (float32 scores, int32 docs): page_cursor's pair")
+        if a_s.shape != (Q,) or a_d.shape != (Q,):
+            raise ValueError(f"after must hold one cursor per query ({Q}), got shapes "
+                             f"{a_s.shape} and {a_d.shape}")
+        a_s, a_d = np.ascontiguousarray(a_s), np.ascontiguousarray(a_d)
+        if a_d.size and int(a_d.min()) < AFTER_NONE:
+            raise ValueError(f"after docs must be >= AFTER_NONE ({AFTER_NONE})")
+        if bool((np.isnan(a_s) & (a_d >= 0)).any()):
+            raise ValueError("after scores must not be NaN where after docs name a document")
+        return a_s, a_d
+
     def search_after(self, queries: np.ndarray, k: int, after=None, weights=None, masks=None,
                      query_mask=None) -> Tuple[np.ndarray, np.ndarray]:
         """The next k results after a cursor (bm25_search_after, host arrays):
@@ -793,41 +826,11 @@ class GpuIndex:
         ascending; global ids).  after_docs[q] == AFTER_NONE: no cursor for
         that row; -1: the list is exhausted, the row is all padding.  weights
         (None: plain sums), masks and query_mask as in search_weighted."""
-        q = np.ascontiguousarray(queries, dtype=np.int32)
-        if q.ndim != 2:
-            raise ValueError("queries must be a 2-D [Q, T] int32 array")
+        q, w, m, M, qm = self._ranked_args(queries, weights, masks, query_mask)
         Q, T = q.shape
-        w = None if weights is None else self._weights_arg(q, weights)
-        m = None if masks is None else self._masks_arg(masks)
-        M = 0 if m is None else m.shape[0]
-        qm = None
-        if query_mask is not None:
-            qm = np.ascontiguousarray(query_mask, dtype=np.int32)
-            if qm.ndim != 1 or qm.size != Q:
-                raise ValueError(f"query_mask must hold one mask id per query ({Q}), "
-                                 f"got shape {qm.shape}")
-            if qm.size and (int(qm.min()) < -1 or int(qm.max()) >= M):
-                raise ValueError(f"query_mask entries must be in [-1, {M})")
-        a_s = a_d = None
-        if after is not None:
-            if not isinstance(after, (tuple, list)) or len(after) != 2:
-                raise ValueError("after must be None or a pair (scores [Q], docs [Q])")
-            if after[0] is None or after[1] is None:
-                raise ValueError("after needs both halves: (scores [Q], docs [Q])")
-            a_s, a_d = np.asarray(after[0]), np.asarray(after[1])
-            if a_s.dtype != np.float32 or a_d.dtype != np.int32:
-                raise ValueError("after must be (float32 scores, int32 docs): page_cursor's pair")
-            if a_s.shape != (Q,) or a_d.shape != (Q,):
-                raise ValueError(f"after must hold one cursor per query ({Q}), got shapes "
-                                 f"{a_s.shape} and {a_d.shape}")
-            a_s, a_d = np.ascontiguousarray(a_s), np.ascontiguousarray(a_d)
-            if a_d.size and int(a_d.min()) < AFTER_NONE:
-                raise ValueError(f"after docs must be >= AFTER_NONE ({AFTER_NONE})")
-            if bool((np.isnan(a_s) & (a_d >= 0)).any()):
-                raise ValueError("after scores must not be NaN where after docs name a document")
+        a_s, a_d = self._after_arg(after, Q)
         k = int(k)
-        docs = np.zeros((Q, max(k, 0)), np.int32)
-        scores = np.zeros((Q, max(k, 0)), np.float32)
+        docs, scores = _topk_out(Q, k)
         check(lib.bm25_search_after(self._h, _ptr(q), _ptr(w), Q, T, k, _ptr(m) if M else None, M,
                                     _ptr(qm), _ptr(a_s), _ptr(a_d), _ptr(docs), _ptr(scores)))
         return docs, scores
@@ -841,21 +844,7 @@ class GpuIndex:
         enqueued on ``stream``.  No validation: an after-docs entry < -1 is
         "no cursor", a NaN cursor score leaves its row unspecified.  It may
         synchronise ``stream`` once, as search_filtered_device."""
-        if d_queries.dim() != 2:
-            raise ValueError("d_queries must be a 2-D [Q, T] tensor")
-        Q, T = d_queries.shape
-        if d_weights is not None and (
-                tuple(d_weights.shape) != (Q, T) or not d_weights.dtype.is_floating_point
-                or d_weights.element_size() != 4):
-            raise ValueError(f"d_weights must be a float32 [{Q}, {T}] tensor")
-        W = (self.n_docs + 31) // 32
-        M = 0
-        if d_masks is not None:
-            if d_masks.dim() != 2 or d_masks.shape[1] != W or d_masks.element_size() != 4:
-                raise ValueError(f"d_masks must be a packed [M, {W}] tensor of 32-bit words")
-            M = d_masks.shape[0]
-        if d_query_mask is not None and d_query_mask.numel() != Q:
-            raise ValueError(f"d_query_mask must hold one mask id per query ({Q})")
+        Q, T, M = self._ranked_device_args(d_queries, d_weights, d_masks, d_query_mask)
         a_s = a_d = None
         if d_after is not None:
             if not isinstance(d_after, (tuple, list)) or len(d_after) != 2:
@@ -869,13 +858,11 @@ class GpuIndex:
                     or not a_s.is_contiguous() or not a_d.is_contiguous()):
                 raise ValueError(f"d_after must be contiguous (float32 [{Q}], int32 [{Q}]) tensors")
         k = int(k)
-        if d_docs.numel() != Q * k or d_scores.numel() != Q * k:
-            raise ValueError(f"d_docs and d_scores must hold {Q} x {k} results")
-        s = getattr(stream, "cuda_stream", stream) or 0
-        vp = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        self._device_out(d_docs, d_scores, Q, k)
         check(lib.bm25_search_after_device(
-            self._h, vp(d_queries), vp(d_weights), Q, T, k, vp(d_masks) if M else None, M,
-            vp(d_query_mask), vp(a_s), vp(a_d), vp(d_docs), vp(d_scores), ctypes.c_void_p(s)))
+            self._h, _dptr(d_queries), _dptr(d_weights), Q, T, k, _dptr(d_masks) if M else None, M,
+            _dptr(d_query_mask), _dptr(a_s), _dptr(a_d), _dptr(d_docs), _dptr(d_scores),
+            ctypes.c_void_p(_stream(stream))))
 
     # ------------------------------------------------------ field collapsing
     COLLAPSE_MAX_K = 4096   # the per-row group table lives in LDS
@@ -902,21 +889,8 @@ class GpuIndex:
         query_mask as in search_after.  k <= 4096.  Returns (docs, scores), and
         the hits' groups (-1 in padding) as a third array with
         ``return_groups``."""
-        q = np.ascontiguousarray(queries, dtype=np.int32)
-        if q.ndim != 2:
-            raise ValueError("queries must be a 2-D [Q, T] int32 array")
+        q, w, m, M, qm = self._ranked_args(queries, weights, masks, query_mask)
         Q, T = q.shape
-        w = None if weights is None else self._weights_arg(q, weights)
-        m = None if masks is None else self._masks_arg(masks)
-        M = 0 if m is None else m.shape[0]
-        qm = None
-        if query_mask is not None:
-            qm = np.ascontiguousarray(query_mask, dtype=np.int32)
-            if qm.ndim != 1 or qm.size != Q:
-                raise ValueError(f"query_mask must hold one mask id per query ({Q}), "
-                                 f"got shape {qm.shape}")
-            if qm.size and (int(qm.min()) < -1 or int(qm.max()) >= M):
-                raise ValueError(f"query_mask entries must be in [-1, {M})")
         g = np.asarray(groups)
         if g.dtype.kind not in "iu" or g.ndim != 1 or g.size != self.n_docs:
             raise ValueError(f"groups must be an integer array of {self.n_docs} (n_docs) entries, "
@@ -925,8 +899,7 @@ class GpuIndex:
             raise ValueError("groups must fit int32")
         g = np.ascontiguousarray(g, dtype=np.int32)
         k, per_group = self._collapse_args(k, per_group)
-        docs = np.zeros((Q, max(k, 0)), np.int32)
-        scores = np.zeros((Q, max(k, 0)), np.float32)
+        docs, scores = _topk_out(Q, k)
         og = np.zeros((Q, max(k, 0)), np.int32) if return_groups else None
         check(lib.bm25_search_collapsed(self._h, _ptr(q), _ptr(w), Q, T, k,
                                         _ptr(m) if M else None, M, _ptr(qm), _ptr(g), per_group,
@@ -944,36 +917,19 @@ class GpuIndex:
         token ids, weights or mask ids.  It synchronises ``stream`` once per
         round (one round where no row's first 2 k results overfill a
         group)."""
-        if d_queries.dim() != 2:
-            raise ValueError("d_queries must be a 2-D [Q, T] tensor")
-        Q, T = d_queries.shape
-        if d_weights is not None and (
-                tuple(d_weights.shape) != (Q, T) or not d_weights.dtype.is_floating_point
-                or d_weights.element_size() != 4):
-            raise ValueError(f"d_weights must be a float32 [{Q}, {T}] tensor")
-        W = (self.n_docs + 31) // 32
-        M = 0
-        if d_masks is not None:
-            if d_masks.dim() != 2 or d_masks.shape[1] != W or d_masks.element_size() != 4:
-                raise ValueError(f"d_masks must be a packed [M, {W}] tensor of 32-bit words")
-            M = d_masks.shape[0]
-        if d_query_mask is not None and d_query_mask.numel() != Q:
-            raise ValueError(f"d_query_mask must hold one mask id per query ({Q})")
+        Q, T, M = self._ranked_device_args(d_queries, d_weights, d_masks, d_query_mask)
         if (d_groups.dim() != 1 or d_groups.numel() != self.n_docs or d_groups.element_size() != 4
                 or d_groups.dtype.is_floating_point or not d_groups.is_contiguous()):
             raise ValueError(f"d_groups must be a contiguous int32 [{self.n_docs}] (n_docs) tensor")
         k, per_group = self._collapse_args(k, per_group)
-        if d_docs.numel() != Q * k or d_scores.numel() != Q * k:
-            raise ValueError(f"d_docs and d_scores must hold {Q} x {k} results")
+        self._device_out(d_docs, d_scores, Q, k)
         if d_groups_out is not None and (d_groups_out.numel() != Q * k
                                          or d_groups_out.element_size() != 4):
             raise ValueError(f"d_groups_out must hold {Q} x {k} int32 groups")
-        s = getattr(stream, "cuda_stream", stream) or 0
-        vp = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
         check(lib.bm25_search_collapsed_device(
-            self._h, vp(d_queries), vp(d_weights), Q, T, k, vp(d_masks) if M else None, M,
-            vp(d_query_mask), vp(d_groups), per_group, vp(d_docs), vp(d_scores),
-            vp(d_groups_out), ctypes.c_void_p(s)))
+            self._h, _dptr(d_queries), _dptr(d_weights), Q, T, k, _dptr(d_masks) if M else None, M,
+            _dptr(d_query_mask), _dptr(d_groups), per_group, _dptr(d_docs), _dptr(d_scores),
+            _dptr(d_groups_out), ctypes.c_void_p(_stream(stream))))
 
     def collapse_stats(self) -> dict:
         """Counters of the last collapsed search (bm25_search_collapsed_stats):
@@ -1020,7 +976,7 @@ class GpuIndex:
         C = d_docs.shape[1]
         if d_scores.numel() != Q * C:
             raise ValueError(f"d_scores must hold {Q} x {C} scores")
-        s = getattr(stream, "cuda_stream", stream) or 0
+        s = _stream(stream)
         check(lib.bm25_score_docs_weighted_device(
             self._h, ctypes.c_void_p(d_queries.data_ptr()), ctypes.c_void_p(d_weights.data_ptr()),
             Q, T, ctypes.c_void_p(d_docs.data_ptr()), C, ctypes.c_void_p(d_scores.data_ptr()),
@@ -1122,7 +1078,7 @@ class GpuIndex:
             Mb = d_base.shape[0]
             if Mb not in (1, M):
                 raise ValueError(f"d_base has {Mb} rows, expected 1 or {M}")
-        s = getattr(stream, "cuda_stream", stream) or 0
+        s = _stream(stream)
         if d_min_match is None:
             check(lib.bm25_term_masks_device(
                 self._h, *args, M, ctypes.c_void_p(d_base.data_ptr()) if Mb else None, Mb,
@@ -1157,7 +1113,7 @@ class GpuIndex:
             raise ValueError(f"d_counts must be an int64 [{M}] tensor (one count per mask)")
         if not d_masks.is_contiguous():
             raise ValueError("d_masks must be contiguous")
-        s = getattr(stream, "cuda_stream", stream) or 0
+        s = _stream(stream)
         check(lib.bm25_mask_count_device(
             self._h, ctypes.c_void_p(d_masks.data_ptr()) if M and W else None, M,
             ctypes.c_void_p(d_counts.data_ptr()) if M else None, ctypes.c_void_p(s)))
@@ -1201,7 +1157,7 @@ class GpuIndex:
             raise ValueError(f"d_counts must be an int64 [{M}, {G}] tensor (one row per mask)")
         if not d_masks.is_contiguous():
             raise ValueError("d_masks must be contiguous")
-        s = getattr(stream, "cuda_stream", stream) or 0
+        s = _stream(stream)
         check(lib.bm25_mask_facets_device(
             self._h, ctypes.c_void_p(d_masks.data_ptr()) if M and W else None, M,
             ctypes.c_void_p(d_groups.data_ptr()) if self.n_docs else None, G,
@@ -1276,7 +1232,7 @@ class GpuIndex:
             Mb = d_base.shape[0]
             if Mb not in (1, M):
                 raise ValueError(f"d_base has {Mb} rows, expected 1 or {M}")
-        s = getattr(stream, "cuda_stream", stream) or 0
+        s = _stream(stream)
         p = lambda t, n: ctypes.c_void_p(t.data_ptr()) if n else None
         check(lib.bm25_range_masks_device(
             self._h, p(d_values, F and self.n_docs), kinds[d_values.dtype], F, p(d_fields, M * C),
@@ -1318,7 +1274,7 @@ class GpuIndex:
             if (t.dtype != torch.int32 or tuple(t.shape) != (self.n_docs,)
                     or not t.is_contiguous()):
                 raise ValueError(f"{name} must be a contiguous int32 [{self.n_docs}] tensor")
-        s = getattr(stream, "cuda_stream", stream) or 0
+        s = _stream(stream)
         p = lambda t: ctypes.c_void_p(t.data_ptr()) if self.n_docs else None
         check(lib.bm25_sort_ranks_device(self._h, p(d_values), kinds[d_values.dtype],
                                          1 if descending else 0, p(d_ranks), p(d_perm),
@@ -1393,7 +1349,7 @@ class GpuIndex:
             if not d_scratch.is_contiguous():
                 raise ValueError("d_scratch must be contiguous")
             nbytes = d_scratch.numel() * d_scratch.element_size()
-        s = getattr(stream, "cuda_stream", stream) or 0
+        s = _stream(stream)
         p = lambda t, n=1: ctypes.c_void_p(t.data_ptr()) if t is not None and n else None
         check(lib.bm25_search_sorted_device(
             self._h, p(d_masks, M and W), M, p(d_ranks), p(d_perm), k, p(d_after, M),
@@ -1443,8 +1399,7 @@ class GpuIndex:
             rv, kind, rf, rlo, rhi = _range_args(*_ranges_arg(ranges), self.n_docs, rows=Q,
                                                  what="query")
         k = int(k)
-        docs = np.zeros((Q, max(k, 0)), np.int32)
-        scores = np.zeros((Q, max(k, 0)), np.float32)
+        docs, scores = _topk_out(Q, k)
         if ranges is not None:
             totals = np.zeros(Q, np.int64) if total_hits else None
             counts = np.zeros((Q, G), np.int64) if facets is not None else None
@@ -1638,7 +1593,7 @@ class GpuIndex:
 def merge_topk_device(device: int, d_docs, d_scores, W: int, Q: int, k: int, d_out_docs,
                       d_out_scores, stream=None) -> None:
     """Merge W per-shard [Q, k] lists (global doc ids) -> [Q, k] on the GPU."""
-    s = getattr(stream, "cuda_stream", stream) or 0
+    s = _stream(stream)
     check(lib.bm25_merge_topk_device(int(device), ctypes.c_void_p(d_docs.data_ptr()),
                                      ctypes.c_void_p(d_scores.data_ptr()), int(W), int(Q), int(k),
                                      ctypes.c_void_p(d_out_docs.data_ptr()),
@@ -1650,7 +1605,7 @@ def merge_sorted_device(device: int, d_docs, d_scores, W: int, Q: int, k: int, r
                         d_out_docs, d_out_scores, stream=None) -> None:
     """W-way merge of best-first [Q, k] lists (bm25_merge_sorted_device):
     rank w's lists start at element w * rank_stride of d_docs / d_scores."""
-    s = getattr(stream, "cuda_stream", stream) or 0
+    s = _stream(stream)
     check(lib.bm25_merge_sorted_device(int(device), ctypes.c_void_p(d_docs.data_ptr()),
                                        ctypes.c_void_p(d_scores.data_ptr()), int(W), int(Q),
                                        int(k), int(rank_stride),
@@ -1667,7 +1622,7 @@ def merge_collapsed_device(device: int, d_docs, d_scores, d_groups, W: int, Q: i
     writes with d_groups_out — merged in key order and walked once more under
     per_group.  Rank w's lists start at element w * rank_stride of d_docs /
     d_scores / d_groups; d_out_groups is optional."""
-    s = getattr(stream, "cuda_stream", stream) or 0
+    s = _stream(stream)
     ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)
     check(lib.bm25_merge_collapsed_device(int(device), ptr(d_docs), ptr(d_scores), ptr(d_groups),
                                           int(W), int(Q), int(k), int(rank_stride), int(per_group),
@@ -1713,8 +1668,7 @@ class ShardedIndex:
             raise ValueError("queries must be a 2-D [Q, T] int32 array")
         Q, T = q.shape
         k = int(k)
-        docs = np.zeros((Q, max(k, 0)), np.int32)
-        scores = np.zeros((Q, max(k, 0)), np.float32)
+        docs, scores = _topk_out(Q, k)
         check(lib.bm25_sharded_search(self._h, _ptr(q), Q, T, k, _ptr(docs), _ptr(scores)))
         return docs, scores
 

@@ -397,6 +397,29 @@ void alloc_report(bm25_index* h) {
   }
 }
 
+// Grows a device buffer the handle keeps for its next searches (the large-k
+// scratch, the collapsed search's state) to `need` bytes.  Earlier searches
+// may still be using the old one: the host waits for their stream first.  A
+// size is 0 while its buffer is gone, as ensure_io's.
+int grow_kept(bm25_index* h, char*& p, size_t& bytes, size_t need, const char* what) {
+  if (need <= bytes) return BM25_OK;
+  if (h->ws_stream) HIP_TRY(hipStreamSynchronize(h->ws_stream), "hipStreamSynchronize");
+  hipFree(p);
+  p = nullptr;
+  bytes = 0;
+  HIP_TRY(hipMalloc((void**)&p, need), what);
+  bytes = need;
+  return BM25_OK;
+}
+
+// One search in the profile's counts.
+void count_search(bm25_index* h) {
+  if (h->prof) {
+    h->score_launches += 1;
+    h->searches += 1;
+  }
+}
+
 // Device pipeline on stream st; caller holds h->mu and has set the device.
 // shard: bm25_search_shard_device — the collection's threshold from the
 // world bounds and this shard's keys >= it, unsorted, for the W-way merge.
@@ -413,14 +436,9 @@ int run_search(bm25_index* h, const int32_t* d_queries, int64_t Q, int64_t T, in
     }
     // the scratch the large-k paths last asked for, allocated once for the
     // next ones (the device is done with the old arena: its last search is)
-    if (h->arena.need > h->arena.bytes) {
-      if (h->ws_stream) HIP_TRY(hipStreamSynchronize(h->ws_stream), "hipStreamSynchronize");
-      hipFree(h->arena.base);
-      h->arena.base = nullptr;
-      h->arena.bytes = 0;
-      HIP_TRY(hipMalloc((void**)&h->arena.base, h->arena.need), "hipMalloc(large-k scratch)");
-      h->arena.bytes = h->arena.need;
-    }
+    const int rcg =
+        grow_kept(h, h->arena.base, h->arena.bytes, h->arena.need, "hipMalloc(large-k scratch)");
+    if (rcg) return rcg;
     h->arena.used = 0;
     h->ws.arena = &h->arena;
     HIP_TRY(order_ws(h, st), "workspace order");
@@ -446,10 +464,7 @@ int run_search(bm25_index* h, const int32_t* d_queries, int64_t Q, int64_t T, in
       HIP_TRY(hipEventRecord(ev->b, st), "hipEventRecord");
       HIP_TRY(record_end(h, ev, st), "hipEventRecord");
     }
-    if (h->prof) {
-      h->score_launches += 1;
-      h->searches += 1;
-    }
+    count_search(h);
     return BM25_OK;
   }
   int rc = ensure_ws(h, Q, T, k, st);
@@ -468,34 +483,45 @@ int run_search(bm25_index* h, const int32_t* d_queries, int64_t Q, int64_t T, in
   HIP_TRY(launch_select(h->ix, d_queries, Q, T, k, P, h->ws, d_docs, d_scores, st, shard),
           "select launch");
   HIP_TRY(record_end(h, ev, st), "hipEventRecord");
-  if (h->prof) {
-    h->score_launches += 1;
-    h->searches += 1;
-  }
+  count_search(h);
   return BM25_OK;
 }
+
+// The device arrays of a ranked search (RankedArgs' on the device).  A null
+// d_weights: plain sums.  after: the call is bm25_search_after's (the dispatch
+// flag kKAfter), with the cursor arrays d_after_scores / d_after_docs (both
+// null: no cursor).
+struct RankedDev {
+  const int32_t* d_queries = nullptr;
+  const float* d_weights = nullptr;
+  const uint32_t* d_masks = nullptr;
+  int64_t M = 0;
+  const int32_t* d_query_mask = nullptr;
+  bool after = false;
+  const float* d_after_scores = nullptr;
+  const int32_t* d_after_docs = nullptr;
+};
+
+// Bump offsets of 256-byte aligned parts of one allocation of `bytes` bytes.
+struct Carve {
+  size_t bytes = 0;
+  size_t part(int64_t n) {
+    const size_t at = bytes;
+    bytes += ((size_t)n + 255) & ~(size_t)255;
+    return at;
+  }
+};
 
 // The filtered search's device pipeline on stream st (bm25mi_filter.hip);
 // caller holds h->mu and has set the device.  A search of the handle: the
 // workspace, its stream ordering and the large-k scratch as run_search's.
-// after: the call is bm25_search_after's (the dispatch flag kKAfter), with the
-// cursor arrays d_after_scores / d_after_docs (both null: no cursor).
-int run_filtered(bm25_index* h, const int32_t* d_queries, int64_t Q, int64_t T, int k,
-                 const uint32_t* d_masks, int64_t M, const int32_t* d_query_mask, int32_t* d_docs,
-                 float* d_scores, hipStream_t st, const float* d_weights = nullptr,
-                 bool after = false, const float* d_after_scores = nullptr,
-                 const int32_t* d_after_docs = nullptr) {
+int run_filtered(bm25_index* h, int64_t Q, int64_t T, int k, const RankedDev& d, int32_t* d_docs,
+                 float* d_scores, hipStream_t st) {
   if (Q == 0 || k == 0) return BM25_OK;
-  const int rc = ensure_ws(h, Q, T, std::min<int>(k, kMaxK), st);
+  int rc = ensure_ws(h, Q, T, std::min<int>(k, kMaxK), st);
   if (rc) return rc;
-  if (h->arena.need > h->arena.bytes) {
-    if (h->ws_stream) HIP_TRY(hipStreamSynchronize(h->ws_stream), "hipStreamSynchronize");
-    hipFree(h->arena.base);
-    h->arena.base = nullptr;
-    h->arena.bytes = 0;
-    HIP_TRY(hipMalloc((void**)&h->arena.base, h->arena.need), "hipMalloc(filtered scratch)");
-    h->arena.bytes = h->arena.need;
-  }
+  rc = grow_kept(h, h->arena.base, h->arena.bytes, h->arena.need, "hipMalloc(filtered scratch)");
+  if (rc) return rc;
   h->arena.used = 0;
   h->ws.arena = &h->arena;
   HIP_TRY(order_ws(h, st), "workspace order");
@@ -506,20 +532,17 @@ int run_filtered(bm25_index* h, const int32_t* d_queries, int64_t Q, int64_t T, 
   EventPair* ev = next_events(h);
   if (ev) HIP_TRY(hipEventRecord(ev->a, st), "hipEventRecord");
   int64_t nd = 0;
-  if (after) h->ix.disp.kernels |= kKAfter;
-  HIP_TRY(launch_search_filtered(h->ix, d_queries, Q, T, k, d_masks, M, d_query_mask, h->ws,
-                                 d_docs, d_scores, &nd, st, d_weights, d_after_scores,
-                                 d_after_docs),
-          after ? "cursor search" : d_weights ? "weighted search" : "filtered search");
+  if (d.after) h->ix.disp.kernels |= kKAfter;
+  HIP_TRY(launch_search_filtered(h->ix, d.d_queries, Q, T, k, d.d_masks, d.M, d.d_query_mask,
+                                 h->ws, d_docs, d_scores, &nd, st, d.d_weights, d.d_after_scores,
+                                 d.d_after_docs),
+          d.after ? "cursor search" : d.d_weights ? "weighted search" : "filtered search");
   h->filtered_dense = nd;
   if (ev) {
     HIP_TRY(hipEventRecord(ev->b, st), "hipEventRecord");
     HIP_TRY(record_end(h, ev, st), "hipEventRecord");
   }
-  if (h->prof) {
-    h->score_launches += 1;
-    h->searches += 1;
-  }
+  count_search(h);
   return BM25_OK;
 }
 
@@ -547,8 +570,7 @@ struct OwnBuffer {
 // the number of unfinished rows (beside the filtered search's own wait for
 // its overflowed lists).  d_groups_out may be null: the rows' groups are then
 // kept in the state.
-int run_collapsed(bm25_index* h, const int32_t* d_queries, const float* d_weights, int64_t Q,
-                  int64_t T, int k, const uint32_t* d_masks, int64_t M, const int32_t* d_qm,
+int run_collapsed(bm25_index* h, int64_t Q, int64_t T, int k, const RankedDev& d,
                   const int32_t* d_groups, int per_group, int32_t* d_docs, float* d_scores,
                   int32_t* d_groups_out, hipStream_t st) {
   if (Q == 0 || k == 0) return BM25_OK;
@@ -558,23 +580,12 @@ int run_collapsed(bm25_index* h, const int32_t* d_queries, const float* d_weight
       1, std::min<int64_t>(o.collapse_page > 0 ? o.collapse_page : collapse_auto_page(k),
                            std::min<int64_t>(n_docs, kMaxK)));
   // the state of the rows: not the arena's, which run_filtered resets per call
-  size_t need = 0;
-  auto part = [&need](int64_t bytes) {
-    const size_t at = need;
-    need += ((size_t)bytes + 255) & ~(size_t)255;
-    return at;
-  };
-  const size_t o_pd = part(4 * Q * p), o_ps = part(4 * Q * p), o_cs = part(4 * Q),
-               o_cd = part(4 * Q), o_cnt = part(4 * Q), o_rows = part(4 * Q), o_ctr = part(16),
-               o_og = d_groups_out ? 0 : part(4 * Q * k);
-  if (need > h->cstate_bytes) {
-    if (h->ws_stream) HIP_TRY(hipStreamSynchronize(h->ws_stream), "hipStreamSynchronize");
-    hipFree(h->cstate);
-    h->cstate = nullptr;
-    h->cstate_bytes = 0;
-    HIP_TRY(hipMalloc((void**)&h->cstate, need), "hipMalloc(collapse state)");
-    h->cstate_bytes = need;
-  }
+  Carve cs;
+  const size_t o_pd = cs.part(4 * Q * p), o_ps = cs.part(4 * Q * p), o_cs = cs.part(4 * Q),
+               o_cd = cs.part(4 * Q), o_cnt = cs.part(4 * Q), o_rows = cs.part(4 * Q),
+               o_ctr = cs.part(16), o_og = d_groups_out ? 0 : cs.part(4 * Q * k);
+  int rc = grow_kept(h, h->cstate, h->cstate_bytes, cs.bytes, "hipMalloc(collapse state)");
+  if (rc) return rc;
   HIP_TRY(order_ws(h, st), "workspace order");
   char* const b = h->cstate;
   int32_t* pd = (int32_t*)(b + o_pd);
@@ -597,7 +608,9 @@ int run_collapsed(bm25_index* h, const int32_t* d_queries, const float* d_weight
     HIP_TRY(hipStreamSynchronize(st), "collapse round sync");
     return BM25_OK;
   };
-  int rc = run_filtered(h, d_queries, Q, T, p, d_masks, M, d_qm, pd, ps, st, d_weights, true);
+  RankedDev page = d;  // the cursor search, no cursor yet
+  page.after = true;
+  rc = run_filtered(h, Q, T, p, page, pd, ps, st);
   if (rc) return rc;
   rc = walk(nullptr, Q);
   if (rc) return rc;
@@ -610,22 +623,25 @@ int run_collapsed(bm25_index* h, const int32_t* d_queries, const float* d_weight
                                          : std::max<int64_t>(1, ((int64_t)1 << 28) / W);
     chunk = std::min(chunk, U);
     OwnBuffer own;
-    size_t cn = 0;
-    auto cpart = [&cn](int64_t bytes) {
-      const size_t at = cn;
-      cn += ((size_t)bytes + 255) & ~(size_t)255;
-      return at;
-    };
-    const size_t c_q = cpart(4 * chunk * T), c_w = cpart(d_weights ? 4 * chunk * T : 0),
-                 c_as = cpart(4 * chunk), c_ad = cpart(4 * chunk), c_id = cpart(4 * chunk),
-                 c_ex = cpart(4 * chunk * W);
-    HIP_TRY(hipMalloc((void**)&own.p, std::max<size_t>(cn, 256)), "hipMalloc(collapse masks)");
+    Carve cc;
+    const size_t c_q = cc.part(4 * chunk * T), c_w = cc.part(d.d_weights ? 4 * chunk * T : 0),
+                 c_as = cc.part(4 * chunk), c_ad = cc.part(4 * chunk), c_id = cc.part(4 * chunk),
+                 c_ex = cc.part(4 * chunk * W);
+    HIP_TRY(hipMalloc((void**)&own.p, std::max<size_t>(cc.bytes, 256)),
+            "hipMalloc(collapse masks)");
     int32_t* cq = (int32_t*)(own.p + c_q);
-    float* cw = d_weights ? (float*)(own.p + c_w) : nullptr;
+    float* cw = d.d_weights ? (float*)(own.p + c_w) : nullptr;
     float* as = (float*)(own.p + c_as);
     int32_t* ad = (int32_t*)(own.p + c_ad);
     int32_t* ids = (int32_t*)(own.p + c_id);
     uint32_t* excl = (uint32_t*)(own.p + c_ex);
+    // a sub-batch: its rows' queries under their own exclusion masks and cursors
+    page.d_queries = cq;
+    page.d_weights = cw;
+    page.d_masks = excl;
+    page.d_query_mask = ids;
+    page.d_after_scores = as;
+    page.d_after_docs = ad;
     for (int64_t u0 = 0; u0 < U; u0 += chunk) {
       const int64_t n = std::min(chunk, U - u0);
       int64_t live = n, sub = 0;
@@ -635,14 +651,15 @@ int run_collapsed(bm25_index* h, const int32_t* d_queries, const float* d_weight
           return fail(BM25_EHIP, "collapsed search: a row took more than k + 1 = %d rounds", k + 1);
         }
         served += live;
-        HIP_TRY(launch_collapse_gather(rows + u0, n, d_queries, d_weights, T, cur_s, cur_d, cq, cw,
-                                       as, ad, ids, st),
+        HIP_TRY(launch_collapse_gather(rows + u0, n, d.d_queries, d.d_weights, T, cur_s, cur_d, cq,
+                                       cw, as, ad, ids, st),
                 "collapse gather");
-        HIP_TRY(launch_collapse_exclude(rows + u0, n, d_masks, M, d_qm, d_groups, n_docs,
-                                        per_group, k, cnt, og, cur_d, excl, st),
+        HIP_TRY(launch_collapse_exclude(rows + u0, n, d.d_masks, d.M, d.d_query_mask, d_groups,
+                                        n_docs, per_group, k, cnt, og, cur_d, excl, st),
                 "collapse exclusion masks");
         HIP_TRY(hipMemsetAsync(ctr, 0, 8, st), "hipMemsetAsync");
-        rc = run_filtered(h, cq, n, T, p, excl, n, ids, pd, ps, st, cw, true, as, ad);
+        page.M = n;
+        rc = run_filtered(h, n, T, p, page, pd, ps, st);
         if (rc) {
           hipStreamSynchronize(st);
           return rc;
@@ -669,45 +686,6 @@ void read_counters(bm25_index* h, int32_t (&cnt)[kCounters]) {
   ws_wait_host(h);
   hipMemcpyAsync(cnt, h->ws.counters, sizeof cnt, hipMemcpyDeviceToHost, h->stream);
   hipStreamSynchronize(h->stream);
-}
-
-// shard = true: the index is one doc shard of a larger collection, whose
-// [Q, k] lists are padded (doc -1, score bits ~0) where it holds fewer than k
-// documents; otherwise k > n_docs is numpy's argpartition error (the
-// reference's behaviour, bm25_native.py:205).
-int check_k(const bm25_index* h, int64_t k, bool shard = false) {
-  if (k < 0) return fail(BM25_EINVAL, "negative dimensions are not allowed (top_k=%lld)", (long long)k);
-  if (!shard && k > h->ix.n_docs)
-    return fail(BM25_EINVAL, "kth(=%lld) out of bounds (%lld)", (long long)(h->ix.n_docs - k),
-                (long long)h->ix.n_docs);
-  return BM25_OK;
-}
-
-// max(ids, initial = mx), and the reference's check of it
-// (bm25_native.py:116-121: max(initial=0) >= n_terms -> ValueError).
-int64_t max_token(int64_t mx, const int32_t* ids, int64_t n) {
-  for (int64_t i = 0; i < n; ++i) mx = std::max<int64_t>(mx, ids[i]);
-  return mx;
-}
-
-int check_token_ids(int64_t n_terms, int64_t mx0, const int32_t* ids, int64_t n) {
-  const int64_t mx = max_token(mx0, ids, n);
-  if (mx >= n_terms)
-    return fail(BM25_EINVAL,
-                "The maximum token ID in the query (%lld) is higher than the number of tokens in "
-                "the index.",
-                (long long)mx);
-  return BM25_OK;
-}
-
-// The weighted calls' finite-weight rule: a weight on a non-padding slot (a
-// token id >= 0; ids >= n_terms were rejected before) must be finite.
-int check_weights(const int32_t* ids, const float* w, int64_t Q, int64_t T) {
-  for (int64_t i = 0; i < Q * T; ++i)
-    if (ids[i] >= 0 && !std::isfinite(w[i]))
-      return fail(BM25_EINVAL, "weights[%lld][%lld] = %g is not finite", (long long)(i / T),
-                  (long long)(i % T), (double)w[i]);
-  return BM25_OK;
 }
 
 // A call's hold on its handle: the handle's mutex, and its device current
@@ -1068,7 +1046,7 @@ int bm25_search(bm25_index* h, const int32_t* queries, int64_t Q, int64_t T, int
                 int32_t* out_docs, float* out_scores) {
   if (!h) return fail(BM25_EINVAL, "NULL index");
   if (Q < 0 || T < 0) return fail(BM25_EINVAL, "negative query shape");
-  int rc = check_k(h, k);
+  int rc = check_k(h->ix.n_docs, k);
   if (rc) return rc;
   if (Q == 0 || k == 0) return BM25_OK;
   if (T > 0 && !queries) return fail(BM25_EINVAL, "NULL queries");
@@ -1091,7 +1069,7 @@ int bm25_search_device(bm25_index* h, const int32_t* d_queries, int64_t Q, int64
                        int32_t* d_docs, float* d_scores, void* stream) {
   if (!h) return fail(BM25_EINVAL, "NULL index");
   if (Q < 0 || T < 0) return fail(BM25_EINVAL, "negative query shape");
-  int rc = check_k(h, k);
+  int rc = check_k(h->ix.n_docs, k);
   if (rc) return rc;
   if (Q == 0 || k == 0) return BM25_OK;
   Enter in(h);
@@ -1099,43 +1077,61 @@ int bm25_search_device(bm25_index* h, const int32_t* d_queries, int64_t Q, int64
   return run_search(h, d_queries, Q, T, k, d_docs, d_scores, (hipStream_t)stream);
 }
 
+// The arguments of a ranked host call on the device: the weights (with `rules`
+// kRankedWeights even where T == 0: the weighted path wants a pointer), masks,
+// mask ids and cursors in staging buffers of the call's own, the queries in
+// the handle's d_q (after ensure_io).
+static RankedDev stage_ranked(bm25_index* h, HostCall& c, const RankedArgs& a, unsigned rules) {
+  const int64_t W = (h->ix.n_docs + 31) >> 5;
+  RankedDev d;
+  if (a.weights || (rules & kRankedWeights)) {
+    float* d_w = c.alloc<float>(a.Q * a.T);
+    c.upload_to(d_w, a.weights, a.Q * a.T);
+    d.d_weights = d_w;
+  }
+  d.d_masks = c.upload(a.masks, a.M * W);
+  d.M = a.M;
+  d.d_query_mask = c.upload(a.query_mask, a.query_mask ? a.Q : 0);
+  d.d_after_scores = c.upload(a.after_scores, a.after_docs ? a.Q : 0);
+  d.d_after_docs = c.upload(a.after_docs, a.after_docs ? a.Q : 0);
+  c.upload_to(h->d_q, a.queries, a.Q * a.T);
+  d.d_queries = h->d_q;
+  d.after = (rules & kRankedCursor) != 0;
+  return d;
+}
+
+// A ranked host call but the collapsed one: validate, stage, run_filtered into
+// the handle's output buffers, download.  what: the call's label in a HIP
+// error's text ("<what> staging" for a failed upload).
+static int ranked_host_call(bm25_index* h, const RankedArgs& a, unsigned rules,
+                            const char* what_staging, const char* what) {
+  if (!h) return fail(BM25_EINVAL, "NULL index");
+  int rc = check_ranked_shape(h->ix.n_docs, a, rules);
+  if (rc) return rc;
+  if (a.Q == 0 || a.k == 0) return BM25_OK;
+  rc = check_ranked_content(h->ix.n_terms, a, rules);
+  if (rc) return rc;
+  Enter in(h);
+  if (in.rc) return in.rc;
+  rc = ensure_io(h, a.Q * a.T, a.Q * (int64_t)a.k);
+  if (rc) return rc;
+  HostCall c(h->stream);
+  const RankedDev d = stage_ranked(h, c, a, rules);
+  if (!c.ok()) return c.finish(what_staging);
+  c.hold(run_filtered(h, a.Q, a.T, a.k, d, h->d_docs, h->d_scores, h->stream));
+  c.download(a.out_docs, h->d_docs, a.Q * a.k);
+  c.download(a.out_scores, h->d_scores, a.Q * a.k);
+  return c.finish(what);
+}
+
 int bm25_search_filtered(bm25_index* h, const int32_t* queries, int64_t Q, int64_t T, int32_t k,
                          const uint32_t* masks, int64_t M, const int32_t* query_mask,
                          int32_t* out_docs, float* out_scores) {
-  if (!h) return fail(BM25_EINVAL, "NULL index");
-  if (Q < 0 || T < 0 || M < 0) return fail(BM25_EINVAL, "negative query or mask shape");
-  int rc = check_k(h, k);
-  if (rc) return rc;
-  if (Q == 0 || k == 0) return BM25_OK;
-  if (T > 0 && !queries) return fail(BM25_EINVAL, "NULL queries");
-  if (M > 0 && !masks) return fail(BM25_EINVAL, "NULL masks");
-  if (M == 0 && !query_mask)
-    return fail(BM25_EINVAL, "no masks: query_mask must name -1 (no filter) for every query");
-  if (!out_docs || !out_scores) return fail(BM25_EINVAL, "NULL output");
-  rc = check_token_ids(h->ix.n_terms, 0, queries, Q * T);
-  if (rc) return rc;
-  if (query_mask)
-    for (int64_t i = 0; i < Q; ++i)
-      if (query_mask[i] < -1 || query_mask[i] >= M)
-        return fail(BM25_EINVAL, "query_mask[%lld] = %d is outside [-1, %lld)", (long long)i,
-                    query_mask[i], (long long)M);
-  Enter in(h);
-  if (in.rc) return in.rc;
-  rc = ensure_io(h, Q * T, Q * (int64_t)k);
-  if (rc) return rc;
-  // the masks and mask ids: staging buffers of this call's own
-  const int64_t W = (h->ix.n_docs + 31) >> 5;
-  HostCall c(h->stream);
-  uint32_t* d_masks = M > 0 ? c.alloc<uint32_t>(M * W) : nullptr;
-  int32_t* d_qm = query_mask ? c.alloc<int32_t>(Q) : nullptr;
-  c.upload_to(d_masks, masks, M * W);
-  if (query_mask) c.upload_to(d_qm, query_mask, Q);
-  c.upload_to(h->d_q, queries, Q * T);
-  if (!c.ok()) return c.finish("filtered search staging");
-  c.hold(run_filtered(h, h->d_q, Q, T, k, d_masks, M, d_qm, h->d_docs, h->d_scores, h->stream));
-  c.download(out_docs, h->d_docs, Q * k);
-  c.download(out_scores, h->d_scores, Q * k);
-  return c.finish("filtered search");
+  RankedArgs a;
+  a.queries = queries, a.Q = Q, a.T = T, a.k = k;
+  a.masks = masks, a.M = M, a.query_mask = query_mask;
+  a.out_docs = out_docs, a.out_scores = out_scores;
+  return ranked_host_call(h, a, kRankedNeedsMask, "filtered search staging", "filtered search");
 }
 
 int bm25_search_filtered_device(bm25_index* h, const int32_t* d_queries, int64_t Q, int64_t T,
@@ -1143,57 +1139,27 @@ int bm25_search_filtered_device(bm25_index* h, const int32_t* d_queries, int64_t
                                 const int32_t* d_query_mask, int32_t* d_docs, float* d_scores,
                                 void* stream) {
   if (!h) return fail(BM25_EINVAL, "NULL index");
-  if (Q < 0 || T < 0 || M < 0) return fail(BM25_EINVAL, "negative query or mask shape");
-  int rc = check_k(h, k);
+  RankedArgs a;
+  a.Q = Q, a.T = T, a.k = k, a.M = M;
+  const int rc = check_ranked_shape(h->ix.n_docs, a, 0);
   if (rc) return rc;
   if (Q == 0 || k == 0) return BM25_OK;
   Enter in(h);
   if (in.rc) return in.rc;
-  return run_filtered(h, d_queries, Q, T, k, d_masks, M, d_query_mask, d_docs, d_scores,
-                      (hipStream_t)stream);
+  RankedDev d;
+  d.d_queries = d_queries;
+  d.d_masks = d_masks, d.M = M, d.d_query_mask = d_query_mask;
+  return run_filtered(h, Q, T, k, d, d_docs, d_scores, (hipStream_t)stream);
 }
 
 int bm25_search_weighted(bm25_index* h, const int32_t* queries, const float* weights, int64_t Q,
                          int64_t T, int32_t k, const uint32_t* masks, int64_t M,
                          const int32_t* query_mask, int32_t* out_docs, float* out_scores) {
-  if (!h) return fail(BM25_EINVAL, "NULL index");
-  if (Q < 0 || T < 0 || M < 0) return fail(BM25_EINVAL, "negative query or mask shape");
-  int rc = check_k(h, k);
-  if (rc) return rc;
-  if (Q == 0 || k == 0) return BM25_OK;
-  if (T > 0 && !queries) return fail(BM25_EINVAL, "NULL queries");
-  if (T > 0 && !weights) return fail(BM25_EINVAL, "NULL weights");
-  if (M > 0 && !masks) return fail(BM25_EINVAL, "NULL masks");
-  if (!out_docs || !out_scores) return fail(BM25_EINVAL, "NULL output");
-  rc = check_token_ids(h->ix.n_terms, 0, queries, Q * T);
-  if (rc) return rc;
-  rc = check_weights(queries, weights, Q, T);
-  if (rc) return rc;
-  if (query_mask)
-    for (int64_t i = 0; i < Q; ++i)
-      if (query_mask[i] < -1 || query_mask[i] >= M)
-        return fail(BM25_EINVAL, "query_mask[%lld] = %d is outside [-1, %lld)", (long long)i,
-                    query_mask[i], (long long)M);
-  Enter in(h);
-  if (in.rc) return in.rc;
-  rc = ensure_io(h, Q * T, Q * (int64_t)k);
-  if (rc) return rc;
-  // the weights, masks and mask ids: staging buffers of this call's own
-  const int64_t W = (h->ix.n_docs + 31) >> 5;
-  HostCall c(h->stream);
-  float* d_w = c.alloc<float>(Q * T);
-  uint32_t* d_masks = M > 0 ? c.alloc<uint32_t>(M * W) : nullptr;
-  int32_t* d_qm = query_mask ? c.alloc<int32_t>(Q) : nullptr;
-  c.upload_to(d_w, weights, Q * T);
-  c.upload_to(d_masks, masks, M * W);
-  if (query_mask) c.upload_to(d_qm, query_mask, Q);
-  c.upload_to(h->d_q, queries, Q * T);
-  if (!c.ok()) return c.finish("weighted search staging");
-  c.hold(run_filtered(h, h->d_q, Q, T, k, d_masks, M, d_qm, h->d_docs, h->d_scores, h->stream,
-                      d_w));
-  c.download(out_docs, h->d_docs, Q * k);
-  c.download(out_scores, h->d_scores, Q * k);
-  return c.finish("weighted search");
+  RankedArgs a;
+  a.queries = queries, a.weights = weights, a.Q = Q, a.T = T, a.k = k;
+  a.masks = masks, a.M = M, a.query_mask = query_mask;
+  a.out_docs = out_docs, a.out_scores = out_scores;
+  return ranked_host_call(h, a, kRankedWeights, "weighted search staging", "weighted search");
 }
 
 int bm25_search_weighted_device(bm25_index* h, const int32_t* d_queries, const float* d_weights,
@@ -1201,8 +1167,9 @@ int bm25_search_weighted_device(bm25_index* h, const int32_t* d_queries, const f
                                 int64_t M, const int32_t* d_query_mask, int32_t* d_docs,
                                 float* d_scores, void* stream) {
   if (!h) return fail(BM25_EINVAL, "NULL index");
-  if (Q < 0 || T < 0 || M < 0) return fail(BM25_EINVAL, "negative query or mask shape");
-  int rc = check_k(h, k);
+  RankedArgs a;
+  a.Q = Q, a.T = T, a.k = k, a.M = M;
+  const int rc = check_ranked_shape(h->ix.n_docs, a, kRankedWeights);
   if (rc) return rc;
   if (Q == 0 || k == 0) return BM25_OK;
   if (T > 0 && (!d_queries || !d_weights)) return fail(BM25_EINVAL, "NULL queries or weights");
@@ -1212,68 +1179,22 @@ int bm25_search_weighted_device(bm25_index* h, const int32_t* d_queries, const f
   if (in.rc) return in.rc;
   // T == 0: no weight is read, but the weighted path still wants a pointer
   static const float none = 0.f;
-  return run_filtered(h, d_queries, Q, T, k, d_masks, M, d_query_mask, d_docs, d_scores,
-                      (hipStream_t)stream, d_weights ? d_weights : &none);
+  RankedDev d;
+  d.d_queries = d_queries, d.d_weights = d_weights ? d_weights : &none;
+  d.d_masks = d_masks, d.M = M, d.d_query_mask = d_query_mask;
+  return run_filtered(h, Q, T, k, d, d_docs, d_scores, (hipStream_t)stream);
 }
 
 int bm25_search_after(bm25_index* h, const int32_t* queries, const float* weights, int64_t Q,
                       int64_t T, int32_t k, const uint32_t* masks, int64_t M,
                       const int32_t* query_mask, const float* after_scores,
                       const int32_t* after_docs, int32_t* out_docs, float* out_scores) {
-  if (!h) return fail(BM25_EINVAL, "NULL index");
-  if (Q < 0 || T < 0 || M < 0) return fail(BM25_EINVAL, "negative query or mask shape");
-  int rc = check_k(h, k);
-  if (rc) return rc;
-  if ((after_scores != nullptr) != (after_docs != nullptr))
-    return fail(BM25_EINVAL, "after_scores and after_docs must both be given or both be NULL");
-  if (Q == 0 || k == 0) return BM25_OK;
-  if (T > 0 && !queries) return fail(BM25_EINVAL, "NULL queries");
-  if (M > 0 && !masks) return fail(BM25_EINVAL, "NULL masks");
-  if (!out_docs || !out_scores) return fail(BM25_EINVAL, "NULL output");
-  rc = check_token_ids(h->ix.n_terms, 0, queries, Q * T);
-  if (rc) return rc;
-  if (weights) {
-    rc = check_weights(queries, weights, Q, T);
-    if (rc) return rc;
-  }
-  if (query_mask)
-    for (int64_t i = 0; i < Q; ++i)
-      if (query_mask[i] < -1 || query_mask[i] >= M)
-        return fail(BM25_EINVAL, "query_mask[%lld] = %d is outside [-1, %lld)", (long long)i,
-                    query_mask[i], (long long)M);
-  if (after_docs)
-    for (int64_t i = 0; i < Q; ++i) {
-      if (after_docs[i] < BM25_AFTER_NONE)
-        return fail(BM25_EINVAL,
-                    "after_docs[%lld] = %d is below BM25_AFTER_NONE (-2): a cursor names a doc "
-                    "id >= 0, -1 (exhausted) or BM25_AFTER_NONE",
-                    (long long)i, after_docs[i]);
-      if (after_docs[i] >= 0 && std::isnan(after_scores[i]))
-        return fail(BM25_EINVAL, "after_scores[%lld] = %g is not a score (the cursor of doc %d)",
-                    (long long)i, (double)after_scores[i], after_docs[i]);
-    }
-  Enter in(h);
-  if (in.rc) return in.rc;
-  rc = ensure_io(h, Q * T, Q * (int64_t)k);
-  if (rc) return rc;
-  // the weights, masks, mask ids and cursors: staging buffers of this call's own
-  const int64_t W = (h->ix.n_docs + 31) >> 5;
-  HostCall c(h->stream);
-  float* d_w = weights ? c.alloc<float>(Q * T) : nullptr;
-  uint32_t* d_masks = M > 0 ? c.alloc<uint32_t>(M * W) : nullptr;
-  int32_t* d_qm = query_mask ? c.alloc<int32_t>(Q) : nullptr;
-  if (weights) c.upload_to(d_w, weights, Q * T);
-  c.upload_to(d_masks, masks, M * W);
-  if (query_mask) c.upload_to(d_qm, query_mask, Q);
-  const float* d_as = c.upload(after_scores, after_docs ? Q : 0);
-  const int32_t* d_ad = c.upload(after_docs, after_docs ? Q : 0);
-  c.upload_to(h->d_q, queries, Q * T);
-  if (!c.ok()) return c.finish("cursor search staging");
-  c.hold(run_filtered(h, h->d_q, Q, T, k, d_masks, M, d_qm, h->d_docs, h->d_scores, h->stream,
-                      d_w, true, d_as, d_ad));
-  c.download(out_docs, h->d_docs, Q * k);
-  c.download(out_scores, h->d_scores, Q * k);
-  return c.finish("cursor search");
+  RankedArgs a;
+  a.queries = queries, a.weights = weights, a.Q = Q, a.T = T, a.k = k;
+  a.masks = masks, a.M = M, a.query_mask = query_mask;
+  a.after_scores = after_scores, a.after_docs = after_docs;
+  a.out_docs = out_docs, a.out_scores = out_scores;
+  return ranked_host_call(h, a, kRankedCursor, "cursor search staging", "cursor search");
 }
 
 int bm25_search_after_device(bm25_index* h, const int32_t* d_queries, const float* d_weights,
@@ -1282,32 +1203,22 @@ int bm25_search_after_device(bm25_index* h, const int32_t* d_queries, const floa
                              const int32_t* d_after_docs, int32_t* d_docs, float* d_scores,
                              void* stream) {
   if (!h) return fail(BM25_EINVAL, "NULL index");
-  if (Q < 0 || T < 0 || M < 0) return fail(BM25_EINVAL, "negative query or mask shape");
-  int rc = check_k(h, k);
+  RankedArgs a;  // (device pointers: looked at, never read)
+  a.queries = d_queries, a.Q = Q, a.T = T, a.k = k, a.masks = d_masks, a.M = M;
+  a.after_scores = d_after_scores, a.after_docs = d_after_docs;
+  a.out_docs = d_docs, a.out_scores = d_scores;
+  int rc = check_ranked_shape(h->ix.n_docs, a, kRankedCursor);
   if (rc) return rc;
-  if ((d_after_scores != nullptr) != (d_after_docs != nullptr))
-    return fail(BM25_EINVAL, "after_scores and after_docs must both be given or both be NULL");
   if (Q == 0 || k == 0) return BM25_OK;
-  if (T > 0 && !d_queries) return fail(BM25_EINVAL, "NULL queries");
-  if (M > 0 && !d_masks) return fail(BM25_EINVAL, "NULL masks");
-  if (!d_docs || !d_scores) return fail(BM25_EINVAL, "NULL output");
+  rc = check_ranked_pointers(a, kRankedCursor);
+  if (rc) return rc;
   Enter in(h);
   if (in.rc) return in.rc;
-  return run_filtered(h, d_queries, Q, T, k, d_masks, M, d_query_mask, d_docs, d_scores,
-                      (hipStream_t)stream, d_weights, true, d_after_scores, d_after_docs);
-}
-
-// The collapsed calls' own argument rules (both the host and the device call).
-static int check_collapse(const bm25_index* h, int64_t Q, int64_t T, int64_t M, int32_t k,
-                          int32_t per_group) {
-  if (Q < 0 || T < 0 || M < 0) return fail(BM25_EINVAL, "negative query or mask shape");
-  if (k > kMaxK)
-    return fail(BM25_EINVAL,
-                "k=%d: a collapsed search is limited to k <= %d (the per-row group table lives "
-                "in LDS)",
-                k, kMaxK);
-  if (per_group < 1) return fail(BM25_EINVAL, "per_group=%d must be >= 1", per_group);
-  return check_k(h, k);
+  RankedDev d;
+  d.d_queries = d_queries, d.d_weights = d_weights;
+  d.d_masks = d_masks, d.M = M, d.d_query_mask = d_query_mask;
+  d.after = true, d.d_after_scores = d_after_scores, d.d_after_docs = d_after_docs;
+  return run_filtered(h, Q, T, k, d, d_docs, d_scores, (hipStream_t)stream);
 }
 
 int bm25_search_collapsed(bm25_index* h, const int32_t* queries, const float* weights, int64_t Q,
@@ -1315,44 +1226,29 @@ int bm25_search_collapsed(bm25_index* h, const int32_t* queries, const float* we
                           const int32_t* query_mask, const int32_t* groups, int32_t per_group,
                           int32_t* out_docs, float* out_scores, int32_t* out_groups) {
   if (!h) return fail(BM25_EINVAL, "NULL index");
-  int rc = check_collapse(h, Q, T, M, k, per_group);
+  RankedArgs a;
+  a.queries = queries, a.weights = weights, a.Q = Q, a.T = T, a.k = k;
+  a.masks = masks, a.M = M, a.query_mask = query_mask;
+  a.groups = groups, a.per_group = per_group;
+  a.out_docs = out_docs, a.out_scores = out_scores;
+  int rc = check_ranked_shape(h->ix.n_docs, a, kRankedCollapse);
   if (rc) return rc;
   if (Q == 0 || k == 0) return BM25_OK;
-  if (T > 0 && !queries) return fail(BM25_EINVAL, "NULL queries");
-  if (M > 0 && !masks) return fail(BM25_EINVAL, "NULL masks");
-  if (!groups) return fail(BM25_EINVAL, "NULL groups (one int32 per document; < 0: no group)");
-  if (!out_docs || !out_scores) return fail(BM25_EINVAL, "NULL output");
-  rc = check_token_ids(h->ix.n_terms, 0, queries, Q * T);
+  rc = check_ranked_content(h->ix.n_terms, a, kRankedCollapse);
   if (rc) return rc;
-  if (weights) {
-    rc = check_weights(queries, weights, Q, T);
-    if (rc) return rc;
-  }
-  if (query_mask)
-    for (int64_t i = 0; i < Q; ++i)
-      if (query_mask[i] < -1 || query_mask[i] >= M)
-        return fail(BM25_EINVAL, "query_mask[%lld] = %d is outside [-1, %lld)", (long long)i,
-                    query_mask[i], (long long)M);
   Enter in(h);
   if (in.rc) return in.rc;
   rc = ensure_io(h, Q * T, Q * (int64_t)k);
   if (rc) return rc;
-  // the weights, masks, mask ids, groups and the rows' groups: staging buffers
-  // of this call's own
-  const int64_t W = (h->ix.n_docs + 31) >> 5;
+  // beside the ranked arguments, the groups and the rows' groups: staging
+  // buffers of this call's own
   HostCall c(h->stream);
-  float* d_w = weights ? c.alloc<float>(Q * T) : nullptr;
-  uint32_t* d_masks = M > 0 ? c.alloc<uint32_t>(M * W) : nullptr;
-  int32_t* d_qm = query_mask ? c.alloc<int32_t>(Q) : nullptr;
-  if (weights) c.upload_to(d_w, weights, Q * T);
-  c.upload_to(d_masks, masks, M * W);
-  if (query_mask) c.upload_to(d_qm, query_mask, Q);
+  const RankedDev d = stage_ranked(h, c, a, kRankedCollapse);
   const int32_t* d_groups = c.upload(groups, h->ix.n_docs);
   int32_t* d_og = c.alloc<int32_t>(Q * (int64_t)k);
-  c.upload_to(h->d_q, queries, Q * T);
   if (!c.ok()) return c.finish("collapsed search staging");
-  c.hold(run_collapsed(h, h->d_q, d_w, Q, T, k, d_masks, M, d_qm, d_groups, per_group, h->d_docs,
-                       h->d_scores, d_og, h->stream));
+  c.hold(run_collapsed(h, Q, T, k, d, d_groups, per_group, h->d_docs, h->d_scores, d_og,
+                       h->stream));
   c.download(out_docs, h->d_docs, Q * k);
   c.download(out_scores, h->d_scores, Q * k);
   if (out_groups) c.download(out_groups, d_og, Q * k);
@@ -1365,17 +1261,22 @@ int bm25_search_collapsed_device(bm25_index* h, const int32_t* d_queries, const 
                                  int32_t per_group, int32_t* d_docs, float* d_scores,
                                  int32_t* d_groups_out, void* stream) {
   if (!h) return fail(BM25_EINVAL, "NULL index");
-  int rc = check_collapse(h, Q, T, M, k, per_group);
+  RankedArgs a;  // (device pointers: looked at, never read)
+  a.queries = d_queries, a.Q = Q, a.T = T, a.k = k, a.masks = d_masks, a.M = M;
+  a.groups = d_groups, a.per_group = per_group;
+  a.out_docs = d_docs, a.out_scores = d_scores;
+  int rc = check_ranked_shape(h->ix.n_docs, a, kRankedCollapse);
   if (rc) return rc;
   if (Q == 0 || k == 0) return BM25_OK;
-  if (T > 0 && !d_queries) return fail(BM25_EINVAL, "NULL queries");
-  if (M > 0 && !d_masks) return fail(BM25_EINVAL, "NULL masks");
-  if (!d_groups) return fail(BM25_EINVAL, "NULL groups (one int32 per document; < 0: no group)");
-  if (!d_docs || !d_scores) return fail(BM25_EINVAL, "NULL output");
+  rc = check_ranked_pointers(a, kRankedCollapse);
+  if (rc) return rc;
   Enter in(h);
   if (in.rc) return in.rc;
-  return run_collapsed(h, d_queries, d_weights, Q, T, k, d_masks, M, d_query_mask, d_groups,
-                       per_group, d_docs, d_scores, d_groups_out, (hipStream_t)stream);
+  RankedDev d;
+  d.d_queries = d_queries, d.d_weights = d_weights;
+  d.d_masks = d_masks, d.M = M, d.d_query_mask = d_query_mask;
+  return run_collapsed(h, Q, T, k, d, d_groups, per_group, d_docs, d_scores, d_groups_out,
+                       (hipStream_t)stream);
 }
 
 int bm25_search_collapsed_stats(bm25_index* h, int64_t* out, int32_t n) {
@@ -1889,7 +1790,7 @@ int bm25_search_boolean_sorted(bm25_index* h, const int32_t* queries, int64_t Q,
   if (G > 0 && (groups == nullptr) != (out_facets == nullptr))
     return fail(BM25_EINVAL, "facets: groups and out_facets come together (one of them is NULL)");
   if (G == 0 || !groups) out_facets = nullptr;  // (no group: no facet row to write)
-  rc = check_k(h, k);
+  rc = check_k(h->ix.n_docs, k);
   if (rc) return rc;
   if (sorted && k > kMaxK)
     return fail(BM25_EINVAL, "k = %d: a sorted search returns at most %d hits a row", (int)k,
@@ -2002,8 +1903,10 @@ int bm25_search_boolean_sorted(bm25_index* h, const int32_t* queries, int64_t Q,
         c.run(launch_sorted_pad_scores(h->d_docs + q0 * k, h->d_scores + q0 * k, n * k, h->stream));
       continue;
     }
-    c.hold(run_filtered(h, h->d_q + q0 * T, n, T, k, d_masks, n, d_qm, h->d_docs + q0 * k,
-                        h->d_scores + q0 * k, h->stream));
+    RankedDev rows;  // the chunk's queries, each under its own mask
+    rows.d_queries = h->d_q + q0 * T;
+    rows.d_masks = d_masks, rows.M = n, rows.d_query_mask = d_qm;
+    c.hold(run_filtered(h, n, T, k, rows, h->d_docs + q0 * k, h->d_scores + q0 * k, h->stream));
     n_dense += h->filtered_dense;
   }
   if (k > 0 && !by_rank) h->filtered_dense = n_dense;
@@ -2124,7 +2027,7 @@ int bm25_search_shard_device(bm25_index* h, const int32_t* d_queries, int64_t Q,
                              int32_t k, int32_t* d_docs, float* d_scores, void* stream) {
   if (!h) return fail(BM25_EINVAL, "NULL index");
   if (Q < 0 || T < 0) return fail(BM25_EINVAL, "negative query shape");
-  int rc = check_k(h, k, true);
+  int rc = check_k(h->ix.n_docs, k, true);
   if (rc) return rc;
   if (Q == 0 || k == 0) return BM25_OK;
   std::lock_guard<std::mutex> lk(h->mu);
@@ -2173,7 +2076,7 @@ int bm25_search_sample_device(bm25_index* h, const int32_t* d_queries, int64_t Q
                               void* stream) {
   if (!h) return fail(BM25_EINVAL, "NULL index");
   if (Q < 0 || T < 0 || world < 1) return fail(BM25_EINVAL, "bad shape");
-  int rc = check_k(h, k, true);
+  int rc = check_k(h->ix.n_docs, k, true);
   if (rc) return rc;
   if (Q == 0 || k == 0 || k > kMaxK) return BM25_OK;  // k > kMaxK: no sample half
   Enter in(h);
@@ -2204,7 +2107,7 @@ static int finish_impl(bm25_index* h, const int32_t* d_queries, int64_t Q, int64
                        hipStream_t st_sel) {
   if (!h) return fail(BM25_EINVAL, "NULL index");
   if (Q < 0 || T < 0 || world < 1) return fail(BM25_EINVAL, "bad shape");
-  int rc = check_k(h, k, true);
+  int rc = check_k(h->ix.n_docs, k, true);
   if (rc) return rc;
   if (Q == 0 || k == 0) return BM25_OK;
   Enter in(h);
@@ -2256,10 +2159,7 @@ static int finish_impl(bm25_index* h, const int32_t* d_queries, int64_t Q, int64
           "select launch");
   HIP_TRY(record_end(h, ev, st_sel), "hipEventRecord");
   h->ws_stream = st_sel;  // (the next search on another stream waits for this one)
-  if (h->prof) {
-    h->score_launches += 1;
-    h->searches += 1;
-  }
+  count_search(h);
   return BM25_OK;
 }
 

@@ -1,7 +1,8 @@
 // bm25mi_host.h — host-only helpers of the C-ABI boundary (bm25mi_capi.cpp;
 // tests/asan/host_check.cpp drives them without a device): the error
-// reporters, the staging helper of the synchronous host-pointer calls and the
-// table of the search options.  No .hip file includes this.
+// reporters, the staging helper of the synchronous host-pointer calls, the
+// table of the search options and the argument rules that read host arrays.
+// No .hip file includes this.
 //
 // A host entry point reads: validate, Enter (bm25mi_capi.cpp), HostCall,
 // finish.
@@ -9,6 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <vector>
 
@@ -173,6 +175,135 @@ inline int check_after_ranks(const int32_t* after, int64_t M) {
     if (after[m] < BM25_AFTER_NONE)
       return fail(BM25_EINVAL, "after_ranks[%lld] = %d is below BM25_AFTER_NONE (-2)", (long long)m,
                   (int)after[m]);
+  return BM25_OK;
+}
+
+// k of a top-k call.  shard = true: the index is one doc shard of a larger
+// collection, whose [Q, k] lists are padded (doc -1, score bits ~0) where it
+// holds fewer than k documents; otherwise k > n_docs is numpy's argpartition
+// error (the reference's behaviour, bm25_native.py:205).
+inline int check_k(int64_t n_docs, int64_t k, bool shard = false) {
+  if (k < 0) return fail(BM25_EINVAL, "negative dimensions are not allowed (top_k=%lld)", (long long)k);
+  if (!shard && k > n_docs)
+    return fail(BM25_EINVAL, "kth(=%lld) out of bounds (%lld)", (long long)(n_docs - k),
+                (long long)n_docs);
+  return BM25_OK;
+}
+
+// max(ids, initial = mx), and the reference's check of it
+// (bm25_native.py:116-121: max(initial=0) >= n_terms -> ValueError).
+inline int64_t max_token(int64_t mx, const int32_t* ids, int64_t n) {
+  for (int64_t i = 0; i < n; ++i) mx = std::max<int64_t>(mx, ids[i]);
+  return mx;
+}
+
+inline int check_token_ids(int64_t n_terms, int64_t mx0, const int32_t* ids, int64_t n) {
+  const int64_t mx = max_token(mx0, ids, n);
+  if (mx >= n_terms)
+    return fail(BM25_EINVAL,
+                "The maximum token ID in the query (%lld) is higher than the number of tokens in "
+                "the index.",
+                (long long)mx);
+  return BM25_OK;
+}
+
+// The weighted calls' finite-weight rule: a weight on a non-padding slot (a
+// token id >= 0; ids >= n_terms were rejected before) must be finite.
+inline int check_weights(const int32_t* ids, const float* w, int64_t Q, int64_t T) {
+  for (int64_t i = 0; i < Q * T; ++i)
+    if (ids[i] >= 0 && !std::isfinite(w[i]))
+      return fail(BM25_EINVAL, "weights[%lld][%lld] = %g is not finite", (long long)(i / T),
+                  (long long)(i % T), (double)w[i]);
+  return BM25_OK;
+}
+
+// The arguments of a ranked call — the filtered, weighted, cursor and collapsed
+// searches, host or device form — and the rules in which the calls differ.  A
+// call leaves what it does not take at its default, validates with its rule set
+// (check_ranked_shape, the early return for Q == 0 or k == 0, then
+// check_ranked_content or, of device pointers, check_ranked_pointers) and
+// stages from the same struct; a new ranked call adds a field and a rule, not
+// a copy.  (tests/asan/ranked_check.cpp drives every rule set under the
+// sanitizers, without a device)
+struct RankedArgs {
+  const int32_t* queries = nullptr;  // [Q, T]
+  const float* weights = nullptr;    // [Q, T], or null: plain sums
+  int64_t Q = 0, T = 0;
+  int32_t k = 0;
+  const uint32_t* masks = nullptr;  // [M, W]
+  int64_t M = 0;
+  const int32_t* query_mask = nullptr;  // [Q], or null
+  const float* after_scores = nullptr;  // [Q] each, or both null
+  const int32_t* after_docs = nullptr;
+  const int32_t* groups = nullptr;  // [n_docs]
+  int32_t per_group = 1;
+  int32_t* out_docs = nullptr;  // [Q, k]
+  float* out_scores = nullptr;
+};
+enum RankedRules : unsigned {
+  kRankedWeights = 1,    // weights are required, not optional
+  kRankedNeedsMask = 2,  // without masks, query_mask must be given (and name -1 only)
+  kRankedCursor = 4,     // takes after_scores / after_docs
+  kRankedCollapse = 8,   // takes groups / per_group; k <= kMaxK
+};
+
+// What a call checks before its early return: no pointer is looked at.
+inline int check_ranked_shape(int64_t n_docs, const RankedArgs& a, unsigned rules) {
+  if (a.Q < 0 || a.T < 0 || a.M < 0) return fail(BM25_EINVAL, "negative query or mask shape");
+  if (rules & kRankedCollapse) {
+    if (a.k > kMaxK)
+      return fail(BM25_EINVAL,
+                  "k=%d: a collapsed search is limited to k <= %d (the per-row group table lives "
+                  "in LDS)",
+                  a.k, kMaxK);
+    if (a.per_group < 1) return fail(BM25_EINVAL, "per_group=%d must be >= 1", a.per_group);
+  }
+  const int rc = check_k(n_docs, a.k);
+  if (rc) return rc;
+  if ((rules & kRankedCursor) && (a.after_scores != nullptr) != (a.after_docs != nullptr))
+    return fail(BM25_EINVAL, "after_scores and after_docs must both be given or both be NULL");
+  return BM25_OK;
+}
+
+// The NULL rules of a call with Q > 0 and k > 0; nothing is dereferenced.
+inline int check_ranked_pointers(const RankedArgs& a, unsigned rules) {
+  if (a.T > 0 && !a.queries) return fail(BM25_EINVAL, "NULL queries");
+  if ((rules & kRankedWeights) && a.T > 0 && !a.weights) return fail(BM25_EINVAL, "NULL weights");
+  if (a.M > 0 && !a.masks) return fail(BM25_EINVAL, "NULL masks");
+  if ((rules & kRankedNeedsMask) && a.M == 0 && !a.query_mask)
+    return fail(BM25_EINVAL, "no masks: query_mask must name -1 (no filter) for every query");
+  if ((rules & kRankedCollapse) && !a.groups)
+    return fail(BM25_EINVAL, "NULL groups (one int32 per document; < 0: no group)");
+  if (!a.out_docs || !a.out_scores) return fail(BM25_EINVAL, "NULL output");
+  return BM25_OK;
+}
+
+// The host calls' check of their arrays, after the early return: the NULL
+// rules, then token ids, finite weights, mask ids in [-1, M) and cursors (a doc
+// id >= 0 with a score that is no NaN, -1 or BM25_AFTER_NONE).
+inline int check_ranked_content(int64_t n_terms, const RankedArgs& a, unsigned rules) {
+  int rc = check_ranked_pointers(a, rules);
+  if (rc) return rc;
+  rc = check_token_ids(n_terms, 0, a.queries, a.Q * a.T);
+  if (rc) return rc;
+  if (a.weights) {
+    rc = check_weights(a.queries, a.weights, a.Q, a.T);
+    if (rc) return rc;
+  }
+  for (int64_t i = 0; a.query_mask && i < a.Q; ++i)
+    if (a.query_mask[i] < -1 || a.query_mask[i] >= a.M)
+      return fail(BM25_EINVAL, "query_mask[%lld] = %d is outside [-1, %lld)", (long long)i,
+                  a.query_mask[i], (long long)a.M);
+  for (int64_t i = 0; a.after_docs && i < a.Q; ++i) {
+    if (a.after_docs[i] < BM25_AFTER_NONE)
+      return fail(BM25_EINVAL,
+                  "after_docs[%lld] = %d is below BM25_AFTER_NONE (-2): a cursor names a doc "
+                  "id >= 0, -1 (exhausted) or BM25_AFTER_NONE",
+                  (long long)i, a.after_docs[i]);
+    if (a.after_docs[i] >= 0 && std::isnan(a.after_scores[i]))
+      return fail(BM25_EINVAL, "after_scores[%lld] = %g is not a score (the cursor of doc %d)",
+                  (long long)i, (double)a.after_scores[i], a.after_docs[i]);
+  }
   return BM25_OK;
 }
 

@@ -1,10 +1,12 @@
 // Host-side check of libbm25mi's C-ABI under AddressSanitizer (SURVEY.md:235;
 // VERDICT r4 item 8).  Built by tests/test_host.py::test_capi_host_asan with
 // every source compiled for the host only (--cuda-host-only) and
-// -fsanitize=address, and run where no GPU is visible: every argument check,
-// error message and early-exit path of the boundary runs, the device calls
-// fail with EHIP, and ASan reports any out-of-bounds or use-after-free on the
-// way (the process exits non-zero).  The boundary's two internal pieces
+// -fsanitize=address, and run where no GPU is visible: the argument checks,
+// error messages and early-exit paths of the boundary that need no handle run
+// (the ranked searches' rules sit behind one: tests/asan/ranked_check.cpp
+// drives those), the device calls fail with EHIP, and ASan reports any
+// out-of-bounds or use-after-free on the way (the process exits non-zero).
+// The boundary's two internal pieces
 // (csrc/bm25mi_host.h) are driven directly: the HostCall staging helper with
 // every HIP call failing, and the option table behind set_option / get_option.
 #include <cstdio>

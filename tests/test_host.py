@@ -193,10 +193,12 @@ def test_synth_weight_modes_share_postings():
 
 def test_capi_host_asan():
     """SURVEY.md:235 / VERDICT r4 item 8: the C-ABI's host code under
-    AddressSanitizer.  tests/asan/host_check.cpp drives every argument check,
-    error path and NULL-handle rejection of include/bm25mi.h (here, with no GPU
-    visible, the device calls end in EHIP); ASan aborts the run on any
-    out-of-bounds access or use-after-free of the host side."""
+    AddressSanitizer.  tests/asan/host_check.cpp drives the argument checks,
+    error paths and NULL-handle rejections of include/bm25mi.h that need no
+    handle (here, with no GPU visible, the device calls end in EHIP); ASan
+    aborts the run on any out-of-bounds access or use-after-free of the host
+    side.  The rules of the ranked searches, which sit behind the handle, are
+    driven by tests/asan/ranked_check.cpp (tests/test_ranked_args_host.py)."""
     import subprocess
     from bm25mi.build import build_asan_check
     exe = build_asan_check()
