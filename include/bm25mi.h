@@ -908,8 +908,9 @@ int bm25_search_boolean_ranges(bm25_index* idx, const int32_t* queries, int64_t 
  *   call, as the groups and columns do; the masks still never move to the
  *   host.  k > 4096 with ranks is BM25_EINVAL.
  *
- * Out of scope: merging sorted lists of doc shards (ranks are per handle, so
- * a shard merge needs (value, doc) keys); secondary sort keys other than doc
+ * Out of scope: merging sorted lists of doc shards by their ranks (ranks are
+ * per handle; the keyed merge of "Sort-by-field search over doc shards" below
+ * serves shards with (value, doc) keys); secondary sort keys other than doc
  * id; an early-terminating walk of perm for dense masks; k > 4096.
  */
 int bm25_sort_ranks(bm25_index* idx, const void* values, int32_t kind, int32_t descending,
@@ -934,6 +935,104 @@ int bm25_search_boolean_sorted(bm25_index* idx, const int32_t* queries, int64_t 
                                int64_t* out_total_hits, int64_t* out_facets, const int32_t* ranks,
                                const int32_t* perm, const int32_t* after_ranks,
                                int32_t* out_ranks);
+
+/*
+ * Sort-by-field search over doc shards: order keys, collection cursors and a
+ * keyed merge.  A rank is a position in one handle's permutation: rank 17 of
+ * shard 0 and rank 17 of shard 1 say nothing about each other, and a rank
+ * cursor of one shard means nothing on another.  Shards therefore exchange a
+ * collection-wide order key per hit.  Replaces no reference call.
+ *
+ * The order key K(v, kind, descending) is a uint64, the key the rank build of
+ * bm25_sort_ranks sorts by:
+ *   BM25_FIELD_I32: u = (uint32)v ^ 0x80000000; descending: ~u in 32 bits;
+ *                   zero-extended.
+ *   BM25_FIELD_F32, in this order: (1) NaN gives 1 << 32 in both directions;
+ *                   (2) otherwise +-0.0 become bits 0; (3) u = sign ? ~bits :
+ *                   bits | 0x80000000; (4) descending: (uint32)~u.
+ *   BM25_FIELD_I64: u = (uint64)v ^ (1 << 63); descending: ~u.
+ * The collection-wide order of a column is (K ascending, global doc id
+ * ascending); within one handle it is exactly the order bm25_sort_ranks builds.
+ * All ranks of a collection must use the same kind and direction.
+ *
+ * A key travels as two uint32 planes, key_hi = K >> 32 and key_lo = K &
+ * 0xFFFFFFFF, never as an 8-byte word: a packed [3][Q][k] int32 buffer (docs |
+ * key_hi | key_lo) needs no 8-byte alignment and one all-gather moves docs and
+ * keys together (the layout idea of bm25_merge_collapsed_device).
+ * Padding is doc -1 with key_hi = key_lo = 0xFFFFFFFF.  Padding is recognised
+ * by the doc id, never by the key: a real document whose int64 value is
+ * INT64_MAX ascending has the all-ones key and is still returned, ahead of
+ * padding.
+ *
+ * All three calls are device-only and enqueued on `stream`; they never
+ * synchronise, take no scratch and retain nothing, use no atomics on global
+ * memory, are not searches (bm25_search_dispatch, the counters and
+ * bm25_search_filtered_stats stay as they were) and are not ordered against
+ * the handle's searches.  Every argument check runs before any device call.
+ *
+ * bm25_sort_keys_device: d_docs [n] holds global doc ids as
+ *   bm25_search_sorted_device writes them; element i of d_key_hi / d_key_lo
+ *   [n] gets K(values[d_docs[i] - doc_offset]).  A negative doc id, or one
+ *   outside [doc_offset, doc_offset + n_docs), gets the padding key and reads
+ *   no value.  Nothing past n elements is written.  BM25_EINVAL for a NULL
+ *   index, a bad kind, negative n, or a NULL pointer with n > 0; n == 0 is
+ *   BM25_OK without device work.
+ *
+ * bm25_sort_cursor_device: a collection cursor (key, global doc) per row m <
+ *   M into this handle's rank cursor for bm25_search_sorted_device:
+ *     d_after_docs[m] == -1 (the doc of a padding slot: exhausted)  -> -1
+ *     d_after_docs[m] <  -1 (no cursor)            -> BM25_AFTER_NONE (-2)
+ *     d_after_docs[m] >=  0                        -> from c, below
+ *   c = the number of handle-local documents d with (K(values[d]), doc_offset
+ *   + d) <= (key, d_after_docs[m]), the doc part compared in 64 bits, so a
+ *   cursor document of another shard is legal and means what the inequality
+ *   says.  c == 0 gives -2 — not -1, which would end the row — otherwise c - 1.
+ *   A document is then eligible on this shard iff it is strictly after the
+ *   cursor in the collection's order; the cursor need not name an existing
+ *   document.  Method: one binary search per row over d_perm, which is sorted
+ *   by exactly this pair (about log2(n_docs) dependent pairs of loads, one
+ *   thread per row).  M may pass 65535.  d_perm is the caller's and is not
+ *   validated: an entry outside [0, n_docs) makes that row unspecified, no
+ *   value outside the column is read, the other rows are unaffected.
+ *   BM25_EINVAL for a NULL index, a bad kind, negative M, or NULL pointers with
+ *   M > 0; M == 0 is BM25_OK without device work.
+ *
+ * bm25_merge_sort_keys_device: takes no handle.  List w of row q starts at
+ *   element w * rank_stride + q * k of each input pointer: rank_stride = Q * k
+ *   for plain [W, Q, k] arrays, 3 * Q * k with the pointers Q * k apart for the
+ *   packed buffer one all-gather moves.  Each list is strictly ascending by
+ *   (key, doc) with real entries first; the first doc < 0 and everything after
+ *   it is padding and is never read into a result.  Doc ids are unique across
+ *   the lists.  Row q of the outputs [Q, k] is the first k of the union in
+ *   (key, doc) order, the rest padded with doc -1 and keys 0xFFFFFFFF; every
+ *   output slot is written.  W = 1 returns its input, with padding made
+ *   canonical.  The last column (doc, key) of a page is the next page's
+ *   collection cursor.  BM25_EINVAL, the message naming the value: W outside
+ *   1..64 (W > 64: merge in stages), negative Q or k, k > 4096 (the sorted
+ *   search's own limit), rank_stride < Q * k, a NULL input or output pointer
+ *   with a non-empty shape.  k == 0 or Q == 0 is BM25_OK with no device work.
+ *   Q may pass 65535.  A list that breaks the order precondition gives that
+ *   row unspecified contents; the other rows are unaffected, nothing outside
+ *   the caller's buffers is touched, and the kernel ends.
+ *   Method: a workgroup per row folds the lists one after another into an
+ *   accumulator of at most k (key, doc) entries in LDS, each fold a two-way
+ *   merge by ranking truncated at k: about W k log k steps a row.
+ *
+ * Out of scope: secondary sort keys, ordering by several columns, a
+ * host-buffer form of the three calls, W > 64 in one merge, k > 4096.
+ */
+int bm25_sort_keys_device(bm25_index* idx, const void* d_values, int32_t kind, int32_t descending,
+                          const int32_t* d_docs, int64_t n, uint32_t* d_key_hi,
+                          uint32_t* d_key_lo, void* stream);
+int bm25_sort_cursor_device(bm25_index* idx, const void* d_values, int32_t kind,
+                            int32_t descending, const int32_t* d_perm,
+                            const uint32_t* d_after_key_hi, const uint32_t* d_after_key_lo,
+                            const int32_t* d_after_docs, int64_t M, int32_t* d_after_ranks,
+                            void* stream);
+int bm25_merge_sort_keys_device(int device, const int32_t* d_docs, const uint32_t* d_key_hi,
+                                const uint32_t* d_key_lo, int64_t W, int64_t Q, int32_t k,
+                                int64_t rank_stride, int32_t* d_out_docs, uint32_t* d_out_key_hi,
+                                uint32_t* d_out_key_lo, void* stream);
 
 /*
  * bm25.BM25's float64 path (the dense model's API keeps the reference's

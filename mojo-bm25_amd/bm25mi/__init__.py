@@ -13,7 +13,8 @@ from .build import LIB, SYNTH_LIB, build  # noqa: F401
 def __getattr__(name):
     if name in ("GpuIndex", "merge_topk_device", "merge_collapsed_device", "device_count",
                 "pack_mask", "pad_clause", "AFTER_NONE", "page_cursor", "min_match_rows",
-                "facet_codes", "range_rows"):
+                "facet_codes", "range_rows", "merge_sort_keys_device", "sort_keys",
+                "sort_key_values"):
         from . import index
         return getattr(index, name)
     raise AttributeError(name)

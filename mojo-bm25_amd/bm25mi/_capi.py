@@ -111,6 +111,10 @@ _SIGS = {
     "bm25_search_boolean_sorted": ([_P, _P, _I64, _I64, _I32, _P, _I64, _P, _I64, _P, _I64, _P,
                                     _P, _I64, _P, _I64, _P, _I32, _I64, _P, _P, _P, _I64, _P, _P,
                                     _P, _P, _P, _P, _P, _P], ctypes.c_int),
+    "bm25_sort_keys_device": ([_P, _P, _I32, _I32, _P, _I64, _P, _P, _P], ctypes.c_int),
+    "bm25_sort_cursor_device": ([_P, _P, _I32, _I32, _P, _P, _P, _P, _I64, _P, _P], ctypes.c_int),
+    "bm25_merge_sort_keys_device": ([ctypes.c_int, _P, _P, _P, _I64, _I64, _I32, _I64, _P, _P, _P,
+                                     _P], ctypes.c_int),
     "bm25_index_set_values_f64": ([_P, _P], ctypes.c_int),
     "bm25_scores_dense_f64": ([_P, _P, _I64, _P], ctypes.c_int),
     "bm25_topn_f64": ([_P, _P, _I64, _I64, _P, _P], ctypes.c_int),

@@ -419,3 +419,123 @@ def sharded_search_collapsed(index, d_queries: torch.Tensor, k: int, d_groups: t
         merge_collapsed_device(dev.index, g, g[:, 1].view(torch.float32), g[:, 2], world, Q, k,
                                3 * Q * k, per_group, d_docs, d_scores, d_groups_out, stream)
     return d_docs, d_scores, d_groups_out
+
+
+def sharded_search_sorted(index, d_masks: Optional[torch.Tensor], d_values: torch.Tensor, order,
+                          k: int, descending: bool = False, after=None,
+                          d_queries: Optional[torch.Tensor] = None, rows: Optional[int] = None,
+                          stream=None, group: Optional[dist.ProcessGroup] = None):
+    """One rank's sort-by-field search over doc shards: exactly the
+    single-index GpuIndex.search_sorted_device over the whole collection, on
+    every rank, with the hits' order keys in place of their ranks (a rank is a
+    position in one handle's permutation and means nothing on another shard;
+    include/bm25mi.h, "Sort-by-field search over doc shards").
+
+    ``d_masks`` ([M, W] packed words, or None: every document), ``d_values``
+    (the column's slice) and ``order`` = (d_ranks, d_perm), prebuilt by
+    sort_ranks_device for that slice and ``descending``, are by the rank's own
+    documents.  Every rank must pass the same kind (dtype of the column) and
+    the same direction: keys of different kinds or directions do not compare.
+    ``after`` is an optional collection cursor (d_after_docs int32 [M],
+    d_after_keys int32 [2, M]): the last column of the docs and of the keys a
+    previous page returned (a doc of -1 gives an all-padding row, a doc < -1 is
+    no cursor).  M comes from d_masks, else the cursor, else d_queries, else
+    ``rows``.
+
+    Steps, all enqueued on ``stream`` (default: the current stream):
+    sort_cursor_device turns the cursor into this shard's rank cursors;
+    search_sorted_device runs at min(k, n_docs) into a packed int32 [3, M, k]
+    buffer (docs | key_hi | key_lo; a short shard's slice pre-filled with -1);
+    sort_keys_device fills the key planes; one all-gather moves the buffer
+    (12 M k bytes per rank); bm25_merge_sort_keys_device merges the world's
+    lists on (key, doc).  World size 1 skips the collective and the merge and
+    still returns keys, so paging code is the same at every world size.
+
+    Returns (docs [M, k] int32, keys [2, M, k] int32: key_hi and key_lo;
+    padding is doc -1 with keys 0xFFFFFFFF).  With ``d_queries`` ([M, T] token
+    ids) it returns (docs, keys, scores): score_docs_device runs on the merged
+    docs on every rank (a document of another shard scores +0.0f), one more
+    all-gather and a sum over the ranks give every hit's score — exact, as at
+    most one addend per slot is non-zero and none is -0.0f — and the score bits
+    are 0xFFFFFFFF where the doc is -1: the bits search_boolean(sort=...)
+    returns beside its hits on a single index."""
+    if not isinstance(order, (tuple, list)) or len(order) != 2:
+        raise ValueError("order must be a pair (d_ranks, d_perm), as sort_ranks_device fills them")
+    d_ranks, d_perm = order
+    k = int(k)
+    if k < 0:
+        raise ValueError(f"k={k} must be >= 0")
+    d_after_docs = d_after_keys = None
+    if after is not None:
+        if not isinstance(after, (tuple, list)) or len(after) != 2:
+            raise ValueError("after must be a pair (d_after_docs [M], d_after_keys [2, M])")
+        d_after_docs, d_after_keys = after
+    if d_masks is not None:
+        M = int(d_masks.shape[0])
+    elif d_after_docs is not None:
+        M = int(d_after_docs.shape[0])
+    elif d_queries is not None:
+        M = int(d_queries.shape[0])
+    elif rows is not None:
+        M = int(rows)
+    else:
+        raise ValueError("without d_masks, a cursor or d_queries, pass rows")
+    if d_after_docs is not None and (
+            d_after_docs.dtype != torch.int32 or tuple(d_after_docs.shape) != (M,)
+            or d_after_keys.dtype != torch.int32 or tuple(d_after_keys.shape) != (2, M)):
+        raise ValueError(f"after must be int32 tensors (d_after_docs [{M}], d_after_keys [2, {M}])")
+    if d_queries is not None and (d_queries.dim() != 2 or d_queries.shape[0] != M):
+        raise ValueError(f"d_queries must be a 2-D [{M}, T] tensor (one query per row)")
+    world = dist.get_world_size(group)
+    dev = d_values.device
+    if dev.type != "cuda":
+        stream = None
+    elif stream is None:
+        stream = torch.cuda.current_stream(dev)
+    elif not isinstance(stream, torch.cuda.Stream):
+        stream = torch.cuda.ExternalStream(int(stream), device=dev)
+    from . import index as _index
+    with _stream_ctx(stream):
+        d_after = None
+        if d_after_docs is not None:
+            d_after = torch.empty((M,), dtype=torch.int32, device=dev)
+            keys_in = d_after_keys.contiguous()
+            index.sort_cursor_device(d_values, d_perm, keys_in[0], keys_in[1],
+                                     d_after_docs.contiguous(), d_after, descending, stream)
+        pk = torch.empty((3, M, k), dtype=torch.int32, device=dev)
+        ks = min(k, int(index.n_docs))  # (the C call rejects k > n_docs)
+        scratch = None
+        if d_masks is not None and M and ks:
+            scratch = torch.empty((index.sorted_scratch_bytes(M, ks),), dtype=torch.uint8,
+                                  device=dev)
+        if ks == k:
+            index.search_sorted_device(d_masks, d_ranks, d_perm, ks, d_after, pk[0],
+                                       torch.empty((M, ks), dtype=torch.int32, device=dev),
+                                       scratch, stream)
+        else:  # a short shard: its [M, ks] lists, then padding up to k
+            pk[0].fill_(-1)
+            part = torch.empty((2, M, ks), dtype=torch.int32, device=dev)
+            index.search_sorted_device(d_masks, d_ranks, d_perm, ks, d_after, part[0], part[1],
+                                       scratch, stream)
+            pk[0, :, :ks].copy_(part[0])
+        # (docs of -1 get the padding key: every slot of the planes is written)
+        index.sort_keys_device(d_values, pk[0], pk[1], pk[2], descending, stream)
+        if world == 1:
+            docs, keys = pk[0], pk[1:]
+        else:
+            g = _all_gather(pk, group)  # [W, 3, M, k]: one collective for docs and keys
+            assert tuple(g.shape) == (world, 3, M, k) and g.is_contiguous(), tuple(g.shape)
+            out = torch.empty((3, M, k), dtype=torch.int32, device=dev)
+            # the merge reads rank w's docs at w * 3Mk, its key_hi Mk and its key_lo 2Mk later
+            _index.merge_sort_keys_device(dev.index, g, g[:, 1], g[:, 2], world, M, k, 3 * M * k,
+                                          out[0], out[1], out[2], stream)
+            docs, keys = out[0], out[1:]
+        if d_queries is None:
+            return docs, keys
+        scores = torch.empty((M, k), dtype=torch.float32, device=dev)
+        if M and k:
+            index.score_docs_device(d_queries, docs, scores, stream)
+            if world > 1:
+                scores = _all_gather(scores, group).sum(dim=0)
+            scores.view(torch.int32).masked_fill_(docs < 0, -1)  # (score bits 0xFFFFFFFF)
+    return docs, keys, scores

@@ -327,6 +327,52 @@ def _after_ranks_arg(after, rows: int, what: str = "mask row"):
     return np.ascontiguousarray(np.minimum(a, np.iinfo(np.int32).max), dtype=np.int32)
 
 
+def sort_keys(values, descending: bool = False) -> np.ndarray:
+    """The order keys K(v) of a sort column (include/bm25mi.h, "Sort-by-field
+    search over doc shards"), uint64 [n]: what sort_keys_device writes as
+    key_hi = K >> 32 and key_lo = K & 0xFFFFFFFF, on the host — for reading a
+    page's keys and for making collection cursors without a GPU.  values: int32,
+    int64 or float32 exactly.  A column's order is (K ascending, doc id
+    ascending)."""
+    v = np.ascontiguousarray(values)
+    if v.dtype not in _SORT_KINDS:
+        raise ValueError(f"values have dtype {v.dtype.name}: int32, int64 or float32 (nothing is "
+                         "rounded)")
+    if v.dtype == np.int64:
+        u = v.view(np.uint64) ^ np.uint64(1 << 63)
+        return ~u if descending else u
+    if v.dtype == np.int32:
+        u = v.view(np.uint32) ^ np.uint32(0x80000000)
+        return (~u if descending else u).astype(np.uint64)
+    bits = v.view(np.uint32)
+    bits = np.where((bits & np.uint32(0x7FFFFFFF)) == 0, np.uint32(0), bits)  # -0.0 as +0.0
+    u = np.where((bits >> np.uint32(31)) != 0, ~bits, bits | np.uint32(0x80000000))
+    u = (~u if descending else u).astype(np.uint64)
+    return np.where(np.isnan(v), np.uint64(1 << 32), u)
+
+
+def sort_key_values(keys, dtype, descending: bool = False) -> np.ndarray:
+    """The values of order keys: the inverse of sort_keys for a column of
+    ``dtype`` and direction — the identity on every value except that -0.0
+    comes back as +0.0 and every NaN as one NaN."""
+    k = np.ascontiguousarray(keys, dtype=np.uint64)
+    dt = np.dtype(dtype)
+    if dt not in _SORT_KINDS:
+        raise ValueError(f"dtype {dt.name}: int32, int64 or float32")
+    if dt == np.int64:
+        u = ~k if descending else k
+        return (u ^ np.uint64(1 << 63)).view(np.int64)
+    u = k.astype(np.uint32)  # (the low word; a NaN's key is 1 << 32)
+    if descending:
+        u = ~u
+    if dt == np.int32:
+        return (u ^ np.uint32(0x80000000)).view(np.int32)
+    bits = np.where((u >> np.uint32(31)) != 0, u & np.uint32(0x7FFFFFFF), ~u)
+    out = np.ascontiguousarray(bits, dtype=np.uint32).view(np.float32).copy()
+    out[k == np.uint64(1 << 32)] = np.float32("nan")
+    return out
+
+
 def _sorted_k(k, n_docs: int) -> int:
     if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
         raise ValueError("k must be an int")
@@ -1356,6 +1402,80 @@ class GpuIndex:
             p(d_docs, M * k), p(d_out_ranks, M * k), p(d_scratch, nbytes), nbytes,
             ctypes.c_void_p(s)))
 
+    def _sort_column_arg(self, d_values) -> int:
+        """A device sort column of this handle: contiguous [n_docs] int32,
+        int64 or float32 -> its kind."""
+        import torch
+        kinds = {torch.int32: 0, torch.float32: 1, torch.int64: 2}
+        if d_values.dtype not in kinds:
+            raise ValueError(f"d_values has dtype {d_values.dtype}: int32, int64 or float32")
+        if tuple(d_values.shape) != (self.n_docs,) or not d_values.is_contiguous():
+            raise ValueError(f"d_values must be a contiguous [{self.n_docs}] tensor (one entry per "
+                             "document)")
+        return kinds[d_values.dtype]
+
+    def sort_keys_device(self, d_values, d_docs, d_key_hi, d_key_lo, descending: bool = False,
+                         stream=None) -> None:
+        """The order keys of a page of hits (bm25_sort_keys_device): d_docs, a
+        contiguous int32 tensor of global doc ids as search_sorted_device
+        writes them, in; d_key_hi and d_key_lo, contiguous 32-bit tensors of
+        d_docs' shape, out: the two halves of K(d_values[doc - doc_offset])
+        (bm25mi.sort_keys is the host form).  A doc id < 0 or outside this
+        handle's documents gets the padding key 0xFFFFFFFF / 0xFFFFFFFF and
+        reads no value.  Enqueued on ``stream``; no host synchronisation, no
+        scratch; not a search."""
+        import torch
+        kind = self._sort_column_arg(d_values)
+        if d_docs.dtype != torch.int32 or not d_docs.is_contiguous():
+            raise ValueError("d_docs must be a contiguous int32 tensor")
+        for name, t in (("d_key_hi", d_key_hi), ("d_key_lo", d_key_lo)):
+            if (t.element_size() != 4 or t.is_floating_point() or t.shape != d_docs.shape
+                    or not t.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous 32-bit integer tensor of d_docs' "
+                                 f"shape {tuple(d_docs.shape)}")
+        n = d_docs.numel()
+        s = _stream(stream)
+        p = lambda t, c=1: ctypes.c_void_p(t.data_ptr()) if c else None
+        check(lib.bm25_sort_keys_device(self._h, p(d_values, self.n_docs), kind,
+                                        1 if descending else 0, p(d_docs, n), n, p(d_key_hi, n),
+                                        p(d_key_lo, n), ctypes.c_void_p(s)))
+
+    def sort_cursor_device(self, d_values, d_perm, d_after_key_hi, d_after_key_lo, d_after_docs,
+                           d_after_ranks, descending: bool = False, stream=None) -> None:
+        """A collection cursor per row into this handle's rank cursor
+        (bm25_sort_cursor_device): d_after_key_hi, d_after_key_lo (32-bit) and
+        d_after_docs (int32), [M] each — the last (key, global doc) column of
+        a merged page — in; d_after_ranks int32 [M], the ``d_after`` of
+        search_sorted_device, out: -1 for doc -1 (a padding slot: the row is
+        exhausted), -2 for a doc < -1 (no cursor), else the rank of the last
+        of this handle's documents at or before the cursor (-2 when there is
+        none), so exactly the documents strictly after the cursor stay
+        eligible.  d_perm is sort_ranks' perm for (d_values, descending).
+        Enqueued on ``stream``; no host synchronisation; not a search."""
+        import torch
+        kind = self._sort_column_arg(d_values)
+        if (d_perm.dtype != torch.int32 or tuple(d_perm.shape) != (self.n_docs,)
+                or not d_perm.is_contiguous()):
+            raise ValueError(f"d_perm must be a contiguous int32 [{self.n_docs}] tensor")
+        if d_after_docs.dim() != 1:
+            raise ValueError("d_after_docs must be an int32 [M] tensor (one cursor per row)")
+        M = d_after_docs.shape[0]
+        for name, t, i32 in (("d_after_key_hi", d_after_key_hi, False),
+                             ("d_after_key_lo", d_after_key_lo, False),
+                             ("d_after_docs", d_after_docs, True),
+                             ("d_after_ranks", d_after_ranks, True)):
+            if (t.element_size() != 4 or t.is_floating_point() or tuple(t.shape) != (M,)
+                    or not t.is_contiguous() or (i32 and t.dtype != torch.int32)):
+                raise ValueError(f"{name} must be a contiguous {'int32' if i32 else '32-bit integer'}"
+                                 f" [{M}] tensor (one cursor per row)")
+        s = _stream(stream)
+        p = lambda t, c=1: ctypes.c_void_p(t.data_ptr()) if c else None
+        check(lib.bm25_sort_cursor_device(self._h, p(d_values, self.n_docs), kind,
+                                          1 if descending else 0, p(d_perm, self.n_docs),
+                                          p(d_after_key_hi, M), p(d_after_key_lo, M),
+                                          p(d_after_docs, M), M, p(d_after_ranks, M),
+                                          ctypes.c_void_p(s)))
+
     def search_boolean(self, queries: np.ndarray, k: int, must=None, any=None, must_not=None,
                        base=None, *, min_match=None, total_hits: bool = False, facets=None,
                        ranges=None, sort=None, after_ranks=None):
@@ -1627,6 +1747,38 @@ def merge_collapsed_device(device: int, d_docs, d_scores, d_groups, W: int, Q: i
     check(lib.bm25_merge_collapsed_device(int(device), ptr(d_docs), ptr(d_scores), ptr(d_groups),
                                           int(W), int(Q), int(k), int(rank_stride), int(per_group),
                                           ptr(d_out_docs), ptr(d_out_scores), ptr(d_out_groups),
+                                          ctypes.c_void_p(s)))
+
+
+def merge_sort_keys_device(device: int, d_docs, d_key_hi, d_key_lo, W: int, Q: int, k: int,
+                           rank_stride: int, d_out_docs, d_out_key_hi, d_out_key_lo,
+                           stream=None) -> None:
+    """The doc-shard merge of sorted-search lists (bm25_merge_sort_keys_device):
+    W lists [Q, k] of (doc, key_hi, key_lo), each ascending by (key, doc) with
+    padding (doc < 0) last — search_sorted_device's docs with sort_keys_device's
+    planes — merged into the first k of their union, padded with doc -1 and
+    keys 0xFFFFFFFF.  Rank w's lists start at element w * rank_stride of the
+    three inputs (Q * k for plain [W, Q, k] arrays; 3 * Q * k for the packed
+    [W, 3, Q, k] buffer of one all-gather, the inputs being its planes).  All
+    tensors are contiguous-strided 32-bit integers; the outputs hold Q * k
+    elements.  The last column of the outputs is the next page's collection
+    cursor."""
+    W, Q, k, rank_stride = int(W), int(Q), int(k), int(rank_stride)
+    ins = (("d_docs", d_docs), ("d_key_hi", d_key_hi), ("d_key_lo", d_key_lo))
+    outs = (("d_out_docs", d_out_docs), ("d_out_key_hi", d_out_key_hi),
+            ("d_out_key_lo", d_out_key_lo))
+    for name, t in ins + outs:
+        if t is not None and (t.element_size() != 4 or t.is_floating_point()):
+            raise ValueError(f"{name} must be a 32-bit integer tensor, got {t.dtype}")
+    if Q > 0 and k > 0:
+        for name, t in outs:
+            if t is None or t.numel() != Q * k or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous 32-bit [{Q}, {k}] tensor")
+    s = _stream(stream)
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)
+    check(lib.bm25_merge_sort_keys_device(int(device), ptr(d_docs), ptr(d_key_hi), ptr(d_key_lo),
+                                          W, Q, k, rank_stride, ptr(d_out_docs),
+                                          ptr(d_out_key_hi), ptr(d_out_key_lo),
                                           ctypes.c_void_p(s)))
 
 

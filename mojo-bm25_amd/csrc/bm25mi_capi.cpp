@@ -2471,6 +2471,80 @@ int bm25_merge_collapsed_device(int device, const int32_t* d_docs, const float* 
   return BM25_OK;
 }
 
+// Sort-by-field search over doc shards.  Every check precedes the first device
+// call (Enter's hipSetDevice included): a bad call touches no device.
+int bm25_sort_keys_device(bm25_index* h, const void* d_values, int32_t kind, int32_t descending,
+                          const int32_t* d_docs, int64_t n, uint32_t* d_key_hi,
+                          uint32_t* d_key_lo, void* stream) {
+  if (!h) return fail(BM25_EINVAL, "NULL index");
+  const int rc = check_kind(kind);
+  if (rc) return rc;
+  if (n < 0) return fail(BM25_EINVAL, "sort_keys: n=%lld must be >= 0", (long long)n);
+  if (n == 0) return BM25_OK;
+  if (!d_docs) return fail(BM25_EINVAL, "sort_keys: NULL docs");
+  if (!d_key_hi || !d_key_lo) return fail(BM25_EINVAL, "sort_keys: NULL output");
+  if (h->ix.n_docs > 0 && !d_values) return fail(BM25_EINVAL, "sort_keys: NULL values");
+  // reads the caller's buffers only (as bm25_search_sorted_device: no workspace,
+  // no index array, no ordering against the handle's searches)
+  Enter in(h);
+  if (in.rc) return in.rc;
+  HIP_TRY(launch_sort_keys(h->ix, d_values, kind, descending != 0, d_docs, n, d_key_hi, d_key_lo,
+                           (hipStream_t)stream),
+          "sort_keys launch");
+  return BM25_OK;
+}
+
+int bm25_sort_cursor_device(bm25_index* h, const void* d_values, int32_t kind, int32_t descending,
+                            const int32_t* d_perm, const uint32_t* d_after_key_hi,
+                            const uint32_t* d_after_key_lo, const int32_t* d_after_docs, int64_t M,
+                            int32_t* d_after_ranks, void* stream) {
+  if (!h) return fail(BM25_EINVAL, "NULL index");
+  const int rc = check_kind(kind);
+  if (rc) return rc;
+  if (M < 0) return fail(BM25_EINVAL, "sort_cursor: M=%lld must be >= 0", (long long)M);
+  if (M == 0) return BM25_OK;
+  if (!d_after_key_hi || !d_after_key_lo || !d_after_docs)
+    return fail(BM25_EINVAL, "sort_cursor: NULL cursor");
+  if (!d_after_ranks) return fail(BM25_EINVAL, "sort_cursor: NULL output");
+  if (h->ix.n_docs > 0 && (!d_values || !d_perm))
+    return fail(BM25_EINVAL, "sort_cursor: NULL values or perm");
+  Enter in(h);  // (as bm25_sort_keys_device: the caller's buffers only)
+  if (in.rc) return in.rc;
+  HIP_TRY(launch_sort_cursor(h->ix, d_values, kind, descending != 0, d_perm, d_after_key_hi,
+                             d_after_key_lo, d_after_docs, M, d_after_ranks, (hipStream_t)stream),
+          "sort_cursor launch");
+  return BM25_OK;
+}
+
+int bm25_merge_sort_keys_device(int device, const int32_t* d_docs, const uint32_t* d_key_hi,
+                                const uint32_t* d_key_lo, int64_t W, int64_t Q, int32_t k,
+                                int64_t rank_stride, int32_t* d_out_docs, uint32_t* d_out_key_hi,
+                                uint32_t* d_out_key_lo, void* stream) {
+  if (W < 1 || W > 64)
+    return fail(BM25_EINVAL, "merge_sort_keys: W=%lld must be in 1..64 (W > 64: merge in stages)",
+                (long long)W);
+  if (Q < 0) return fail(BM25_EINVAL, "merge_sort_keys: Q=%lld must be >= 0", (long long)Q);
+  if (k < 0) return fail(BM25_EINVAL, "merge_sort_keys: k=%d must be >= 0", k);
+  if (k > kMaxK)
+    return fail(BM25_EINVAL,
+                "merge_sort_keys: k=%d: a sorted search returns at most %d (the row is merged in LDS)",
+                k, kMaxK);
+  if (Q > 0x7FFFFFFF)
+    return fail(BM25_EINVAL, "merge_sort_keys: Q=%lld must be < 2^31", (long long)Q);
+  if (rank_stride < Q * (int64_t)k)
+    return fail(BM25_EINVAL, "merge_sort_keys: rank_stride=%lld must be >= Q * k (%lld)",
+                (long long)rank_stride, (long long)(Q * (int64_t)k));
+  if (Q == 0 || k == 0) return BM25_OK;
+  if (!d_docs || !d_key_hi || !d_key_lo) return fail(BM25_EINVAL, "merge_sort_keys: NULL input");
+  if (!d_out_docs || !d_out_key_hi || !d_out_key_lo)
+    return fail(BM25_EINVAL, "merge_sort_keys: NULL output");
+  HIP_TRY(hipSetDevice(device), "hipSetDevice");
+  HIP_TRY(launch_merge_sort_keys(d_docs, d_key_hi, d_key_lo, W, Q, k, rank_stride, d_out_docs,
+                                 d_out_key_hi, d_out_key_lo, (hipStream_t)stream),
+          "merge_sort_keys launch");
+  return BM25_OK;
+}
+
 int bm25_profile_enable(bm25_index* h, int on) {
   if (!h) return fail(BM25_EINVAL, "NULL index");
   std::lock_guard<std::mutex> lk(h->mu);

@@ -720,6 +720,34 @@ hipError_t launch_merge_collapsed(const int32_t* d_docs, const float* d_scores,
                                   int64_t rank_stride, int32_t per_group, int32_t* d_out_docs,
                                   float* d_out_scores, int32_t* d_out_groups, hipStream_t stream);
 
+// Sort-by-field search over doc shards (bm25mi_sorted_shards.hip;
+// bm25_sort_keys_device / bm25_sort_cursor_device / bm25_merge_sort_keys_device).
+// The order key K of a value is sort_key() of bm25mi_sort_key_dev.h, carried as
+// two uint32 planes (hi, lo); the collection's order is (K, global doc id).
+//   launch_sort_keys: element i < n of the planes = K(d_values[d_docs[i] -
+//     doc_offset]); a doc id < 0 or outside the handle's documents gets the
+//     padding key (all ones) and reads no value.
+//   launch_sort_cursor: d_after_ranks[m] = the rank cursor of
+//     launch_search_sorted for the collection cursor (key, d_after_docs[m]):
+//     -1 for doc -1, -2 for doc < -1, else c - 1 (-2 when c == 0) with c = the
+//     handle's documents at or before the cursor, by a binary search of d_perm.
+//     A d_perm entry outside [0, n_docs) reads no value.
+//   launch_merge_sort_keys: W lists [Q, k] of (doc, key) at element w *
+//     rank_stride of the three inputs, each ascending by (key, doc) up to its
+//     first doc < 0 -> row q = the first k of the union, padded (doc -1, key all
+//     ones).  Every output slot is written.  1 <= W <= 64, k <= kMaxK.
+hipError_t launch_sort_keys(const DevIndex& ix, const void* d_values, int kind, bool descending,
+                            const int32_t* d_docs, int64_t n, uint32_t* d_key_hi,
+                            uint32_t* d_key_lo, hipStream_t stream);
+hipError_t launch_sort_cursor(const DevIndex& ix, const void* d_values, int kind, bool descending,
+                              const int32_t* d_perm, const uint32_t* d_after_hi,
+                              const uint32_t* d_after_lo, const int32_t* d_after_docs, int64_t M,
+                              int32_t* d_after_ranks, hipStream_t stream);
+hipError_t launch_merge_sort_keys(const int32_t* d_docs, const uint32_t* d_key_hi,
+                                  const uint32_t* d_key_lo, int64_t W, int64_t Q, int32_t k,
+                                  int64_t rank_stride, int32_t* d_out_docs, uint32_t* d_out_key_hi,
+                                  uint32_t* d_out_key_lo, hipStream_t stream);
+
 // Largest token id of [n] device ids (0 if none is positive) into *d_out.
 hipError_t launch_max_token(const int32_t* d_queries, int64_t n, int32_t* d_out,
                             hipStream_t stream);

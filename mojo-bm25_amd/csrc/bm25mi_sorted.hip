@@ -37,6 +37,7 @@
 // output do not.  Global atomics are integer adds (histogram bins, list
 // counts).  Plain C++ and vector memory operations throughout.
 #include "bm25mi_internal.h"
+#include "bm25mi_sort_key_dev.h"
 
 #include <algorithm>
 #include <atomic>
@@ -53,27 +54,7 @@ static_assert(kSortedRows <= 64, "a lane per row of the block");
 static_assert(kSortedRoundDocs == (kSoNT / 64) * kSortedSpanDocs, "a round is the waves' spans");
 static_assert(kSortedBins <= kSoNT, "the pick kernel holds a bin per thread");
 
-// ---- rank build -----------------------------------------------------------
-
-__device__ __forceinline__ uint64_t sort_key(int32_t v, bool desc) {
-  const uint32_t u = (uint32_t)v ^ 0x80000000u;
-  return desc ? (uint32_t)~u : u;
-}
-__device__ __forceinline__ uint64_t sort_key(int64_t v, bool desc) {
-  const uint64_t u = (uint64_t)v ^ 0x8000000000000000ull;
-  return desc ? ~u : u;
-}
-__device__ __forceinline__ uint64_t sort_key(float v, bool desc) {
-  if (v != v) return 1ull << 32;  // NaN: no value, after every number in both directions
-  uint32_t u = __float_as_uint(v);
-  if ((u & 0x7FFFFFFFu) == 0u) u = 0u;  // -0.0f orders as +0.0f
-  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return desc ? (uint32_t)~u : u;
-}
-template <class T>
-constexpr int sort_key_bits() {
-  return sizeof(T) == 8 ? 64 : (std::is_floating_point<T>::value ? 33 : 32);
-}
+// ---- rank build (sort_key: bm25mi_sort_key_dev.h) ---------------------------
 
 template <class T>
 __global__ __launch_bounds__(256) void sort_key_kernel(const T* __restrict__ values, int64_t n,
