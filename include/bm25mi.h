@@ -818,6 +818,97 @@ int bm25_search_boolean_ranges(bm25_index* idx, const int32_t* queries, int64_t 
                                int64_t* out_total_hits, int64_t* out_facets);
 
 /*
+ * Field statistics: count, min, max and exact sum of a per-document column
+ * over the documents every allow-mask allows, per mask row and per group (a
+ * "stats" aggregation, and the "terms" + avg / min / max sub-aggregation:
+ * price range and average price of the hits, average rating per category,
+ * oldest and newest matching document per tenant), on the device.  Replaces no
+ * reference call.
+ *   masks  [M, W] uint32, W = ceil(n_docs / 32), the layout of bm25_search_filtered.
+ *          Bits at or past n_docs are ignored even when set.  No word at
+ *          index >= W of a row is read.
+ *   values [n_docs] of kind (BM25_FIELD_I32 / _F32 / _I64), by the handle's own
+ *          documents.  No entry at index >= n_docs is read.
+ *   groups [n_docs] int32 with G buckets.  groups == NULL and G == 0 together
+ *          mean one bucket per row that holds every allowed document; write
+ *          B = 1.  Otherwise B = G.  A document with a negative group, or in
+ *          the device call a group >= G, is in no bucket.  Exactly one of
+ *          (groups == NULL, G == 0) is BM25_EINVAL.
+ *   A document d contributes to bucket (m, b) if and only if bit d of row m is
+ *   set, its bucket is b, and its value is a number: for float32, NaN is "no
+ *   value", the rule of the sort and range calls; +-inf are numbers.
+ *   Outputs, all [M, B], rows contiguous.  Every entry is written and the
+ *   caller need not clear them.  Nothing past M * B entries is touched.
+ *     out_count int64: the number of contributing documents.
+ *     out_min, out_max of the column's dtype.  The comparison is the dtype's
+ *       own: int64 never goes through a float; float32 is compared by the
+ *       order key of "Sort-by-field search over doc shards" below, so
+ *       -0.0f == +0.0f, and a zero result is written as +0.0f.
+ *     out_sum: int32 column: int64, the exact sum.  int64 column: int64, the
+ *       sum modulo 2^64 (numpy's sum(dtype=int64)).  float32 column: float64,
+ *       the exact real sum of the finite contributing values rounded to
+ *       nearest-even once; +0.0 when that sum is zero or nothing contributes;
+ *       if +inf contributes and -inf does not, +inf; the mirror case gives
+ *       -inf; both contributing gives NaN.  The sum cannot overflow: fewer
+ *       than 2^32 addends below 2^128.
+ *     Where out_count is 0, min, max and sum are written as 0 of their type.
+ *     out_min, out_max and out_sum may each be NULL (not wanted); out_count is
+ *     required.
+ *   The float32 sum is computed with integer accumulators only: a finite value
+ *   of biased exponent e is sig * 2^(E - 150) with E = max(e, 1) and sig the
+ *   24-bit significand (the 23-bit field when e = 0); it adds
+ *   +-(sig << (E & 7)), a magnitude below 2^31, to int64 bin E >> 3 of its
+ *   bucket's 32 bins.  A bin of weight 2^(8 b - 150) cannot overflow int64
+ *   below 2^32 addends.  The bins are carry-normalised from low to high into a
+ *   signed multi-limb integer whose magnitude's top 53 bits are rounded to
+ *   nearest-even on the rest, once.  Count, sums and bins are integer adds,
+ *   min and max are integer maxima of order keys: there are no float atomics,
+ *   and the result does not depend on scheduling — it is bit-identical across
+ *   runs, streams, grids and routes, and Python's math.fsum is its oracle.
+ *   Identities: with no NaN in the column, ungrouped out_count ==
+ *   bm25_mask_count; with no NaN in the column, grouped out_count ==
+ *   bm25_mask_facets; for integer kinds, sum_g out_sum[m][g] plus the sum over
+ *   the allowed documents without a group == the ungrouped sum, in wrapping
+ *   int64.
+ *   Doc shards: values, groups and bits are by the handle's own documents.
+ *   Counts add, min and max combine, integer sums add (wrapping).  The float32
+ *   sums of shards are each rounded once: their float64 sum is not bit-equal
+ *   to the collection's.
+ *   The stats calls are not searches: they leave bm25_search_dispatch,
+ *   bm25_search_counters and bm25_search_filtered_stats alone.
+ *   bm25_mask_stats_scratch: *bytes = the scratch of the device call for
+ *     (kind, M, G) = 8 * M * B * (36 for float32, 4 for the integer kinds): at
+ *     most 288 bytes per bucket plus a constant (the constant is 0 today).
+ *   bm25_mask_stats: host buffers, validated, synchronous; allocates its
+ *     scratch itself.  BM25_EINVAL for a NULL index, a bad kind, a negative M
+ *     or G (or G > 2^31 - 1), a NULL pointer with a non-empty shape, the
+ *     groups / G mismatch above, and a groups[d] >= G (the message names d and
+ *     the value, as bm25_mask_facets does).  On any error the outputs are
+ *     untouched.  M == 0 returns BM25_OK without device work; n_docs == 0
+ *     writes zeros.
+ *   bm25_mask_stats_device: device buffers, enqueued on `stream`; checks
+ *     shapes, NULL pointers, the kind and scratch_bytes >=
+ *     bm25_mask_stats_scratch(...) (d_scratch 8-byte aligned), never
+ *     synchronises, retains nothing, reads the caller's buffers only (no
+ *     workspace, no index array) and is not ordered against the handle's
+ *     searches: it may run on its own stream while a search of the same handle
+ *     is in flight.  M may pass 65535.
+ *   Out of scope: a stats= argument of the boolean search (the device calls
+ *   compose: bm25_term_masks_device -> bm25_mask_stats_device), a sharded or
+ *   distributed form, percentiles, variance and histograms, several columns
+ *   per call.
+ */
+int bm25_mask_stats_scratch(const bm25_index* idx, int32_t kind, int64_t M, int64_t G,
+                            int64_t* bytes);
+int bm25_mask_stats(bm25_index* idx, const uint32_t* masks, int64_t M, const void* values,
+                    int32_t kind, const int32_t* groups, int64_t G, int64_t* out_count,
+                    void* out_min, void* out_max, void* out_sum);
+int bm25_mask_stats_device(bm25_index* idx, const uint32_t* d_masks, int64_t M,
+                           const void* d_values, int32_t kind, const int32_t* d_groups, int64_t G,
+                           int64_t* d_count, void* d_min, void* d_max, void* d_sum,
+                           void* d_scratch, int64_t scratch_bytes, void* stream);
+
+/*
  * Sort-by-field search: the documents a mask allows in the order of a
  * per-document column ("newest first", "cheapest first", by tenant id)
  * instead of by score — the exact top-k of a mask by a column, ties broken by

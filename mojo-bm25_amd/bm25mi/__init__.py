@@ -14,7 +14,7 @@ def __getattr__(name):
     if name in ("GpuIndex", "merge_topk_device", "merge_collapsed_device", "device_count",
                 "pack_mask", "pad_clause", "AFTER_NONE", "page_cursor", "min_match_rows",
                 "facet_codes", "range_rows", "merge_sort_keys_device", "sort_keys",
-                "sort_key_values"):
+                "sort_key_values", "STATS_KEYS"):
         from . import index
         return getattr(index, name)
     raise AttributeError(name)

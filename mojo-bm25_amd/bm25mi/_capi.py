@@ -94,6 +94,10 @@ _SIGS = {
                                        _P, _I64, _P, _P, _P], ctypes.c_int),
     "bm25_mask_facets": ([_P, _P, _I64, _P, _I64, _P], ctypes.c_int),
     "bm25_mask_facets_device": ([_P, _P, _I64, _P, _I64, _P, _P], ctypes.c_int),
+    "bm25_mask_stats_scratch": ([_P, _I32, _I64, _I64, _P], ctypes.c_int),
+    "bm25_mask_stats": ([_P, _P, _I64, _P, _I32, _P, _I64, _P, _P, _P, _P], ctypes.c_int),
+    "bm25_mask_stats_device": ([_P, _P, _I64, _P, _I32, _P, _I64, _P, _P, _P, _P, _P, _I64, _P],
+                               ctypes.c_int),
     "bm25_search_boolean_facets": ([_P, _P, _I64, _I64, _I32, _P, _I64, _P, _I64, _P, _I64, _P,
                                     _P, _I64, _P, _I64, _P, _P, _P, _P], ctypes.c_int),
     "bm25_range_masks": ([_P, _P, _I32, _I64, _P, _P, _P, _I64, _I64, _P, _I64, _P], ctypes.c_int),

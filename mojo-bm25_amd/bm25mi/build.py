@@ -20,13 +20,14 @@ SYNTH_LIB = os.path.join(PKG_DIR, "libbm25synth.so")
 
 HIP_SOURCES = ["bm25mi_kernels.hip", "bm25mi_large.hip", "bm25mi_build.hip", "bm25mi_sort.hip",
                "bm25mi_dense.hip", "bm25mi_lookup.hip", "bm25mi_filter.hip", "bm25mi_termmask.hip",
-               "bm25mi_facets.hip", "bm25mi_range.hip", "bm25mi_collapse.hip",
+               "bm25mi_facets.hip", "bm25mi_stats.hip", "bm25mi_range.hip", "bm25mi_collapse.hip",
                "bm25mi_merge_collapse.hip", "bm25mi_sorted.hip", "bm25mi_sorted_shards.hip",
                "bm25mi_capi.cpp"]
 # Every header a source may include: an object older than one of them is stale.
 HEADERS = [os.path.join(CSRC, "bm25mi_internal.h"), os.path.join(CSRC, "bm25mi_host.h"),
            os.path.join(CSRC, "bm25mi_collapse_dev.h"),
            os.path.join(CSRC, "bm25mi_sort_key_dev.h"),
+           os.path.join(CSRC, "bm25mi_stats_sum.h"),
            os.path.join(REPO, "include", "bm25mi.h")]
 ARCH = os.environ.get("BM25_OFFLOAD_ARCH", "gfx950")
 

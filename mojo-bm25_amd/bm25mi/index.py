@@ -263,6 +263,7 @@ AFTER_NONE = -2  # BM25_AFTER_NONE: an after-docs entry that means "no cursor"
 
 SORTED_MAX_K = 4096  # bm25_search_sorted: hits a row, at most (the LDS sort of a row's list)
 _SORT_KINDS = {np.dtype(np.int32): 0, np.dtype(np.float32): 1, np.dtype(np.int64): 2}
+STATS_KEYS = ("count", "min", "max", "sum", "mean")  # the dict GpuIndex.stats returns
 
 
 def _sort_values_arg(values, n_docs: int):
@@ -1208,6 +1209,125 @@ class GpuIndex:
             self._h, ctypes.c_void_p(d_masks.data_ptr()) if M and W else None, M,
             ctypes.c_void_p(d_groups.data_ptr()) if self.n_docs else None, G,
             ctypes.c_void_p(d_counts.data_ptr()) if M and G else None, ctypes.c_void_p(s)))
+
+    def stats(self, masks, values, groups=None, n_groups=0) -> dict:
+        """Field statistics (bm25_mask_stats, host arrays) -> a dict of [M, B]
+        arrays {count, min, max, sum, mean}: of the documents of this handle
+        that mask m allows, whose group is b (groups=None: B = 1, every allowed
+        document) and whose value is a number (a float32 NaN is no value),
+        count int64, min and max of the values' dtype, sum int64 (integer
+        columns; int64 wraps) or float64 (float32 columns: the exact sum of
+        the values rounded once — bit-equal to math.fsum, whatever the
+        scheduling), and mean = float64 sum / count, NaN where count is 0.
+        values: [n_docs] int32, int64 or float32 exactly; masks as mask_count
+        takes them; groups and n_groups as facets takes them."""
+        m = self._masks_arg(masks)
+        v, kind = _sort_values_arg(values, self.n_docs)
+        g, G = (None, 0)
+        if groups is not None:
+            g, G = _facet_groups(groups, n_groups, self.n_docs)
+            if G == 0:
+                raise ValueError("n_groups = 0 with groups: give the number of groups, or "
+                                 "groups=None for one bucket per mask")
+        elif n_groups != 0:
+            raise ValueError(f"n_groups = {n_groups} without groups")
+        M, B = m.shape[0], G or 1
+        out = {"count": np.zeros((M, B), np.int64), "min": np.zeros((M, B), v.dtype),
+               "max": np.zeros((M, B), v.dtype),
+               "sum": np.zeros((M, B), np.float64 if v.dtype.kind == "f" else np.int64)}
+        p = lambda a: _ptr(a) if a is not None and a.size else None
+        # (grouped with no document: a non-NULL groups pointer still says "grouped")
+        pg = None if g is None else _ptr(g if g.size else np.zeros(1, np.int32))
+        check(lib.bm25_mask_stats(self._h, p(m), M, p(v), kind, pg, G, p(out["count"]),
+                                  p(out["min"]), p(out["max"]), p(out["sum"])))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out["mean"] = np.where(out["count"] > 0,
+                                   out["sum"].astype(np.float64) / out["count"], np.nan)
+        return out
+
+    def stats_scratch_bytes(self, dtype, M: int, n_groups: int = 0) -> int:
+        """Bytes of the d_scratch of stats_device for a column dtype (int32,
+        int64 or float32), M mask rows and n_groups (0: ungrouped)
+        (bm25_mask_stats_scratch)."""
+        dt = np.dtype(dtype)
+        if dt not in _SORT_KINDS:
+            raise ValueError(f"dtype {dt.name}: int32, int64 or float32")
+        b = ctypes.c_int64(0)
+        check(lib.bm25_mask_stats_scratch(self._h, _SORT_KINDS[dt], int(M), int(n_groups),
+                                          ctypes.byref(b)))
+        return int(b.value)
+
+    def stats_device(self, d_masks, d_values, d_count, d_min=None, d_max=None, d_sum=None,
+                     d_groups=None, n_groups=0, d_scratch=None, stream=None) -> None:
+        """Device-resident stats (bm25_mask_stats_device): packed masks [M, W]
+        (32-bit words), a column [n_docs] (int32, int64 or float32) and
+        optionally int32 groups [n_docs] in; d_count int64 [M, B] and, each
+        optional, d_min / d_max [M, B] of the column's dtype and d_sum [M, B]
+        (int64, or float64 for a float32 column) out, B = n_groups or 1; they
+        need not be cleared.  d_scratch: a contiguous tensor of at least
+        stats_scratch_bytes(dtype, M, n_groups) bytes, 8-byte aligned (None:
+        allocated here, on the current device).  Enqueued on ``stream`` with no
+        host synchronisation.  A group id outside [0, n_groups) is in no
+        bucket.  Reads the caller's tensors only, so it may overlap a search of
+        the same handle."""
+        import torch
+        W = (self.n_docs + 31) // 32
+        kinds = {torch.int32: 0, torch.float32: 1, torch.int64: 2}
+        if d_masks.dim() != 2 or d_masks.shape[1] != W or d_masks.element_size() != 4:
+            raise ValueError(f"d_masks must be a packed [M, {W}] tensor of 32-bit words")
+        if not d_masks.is_contiguous():
+            raise ValueError("d_masks must be contiguous")
+        M = d_masks.shape[0]
+        if d_values.dtype not in kinds:
+            raise ValueError(f"d_values has dtype {d_values.dtype}: int32, int64 or float32")
+        if d_values.dim() != 1 or d_values.shape[0] != self.n_docs or not d_values.is_contiguous():
+            raise ValueError(f"d_values must be a contiguous [{self.n_docs}] tensor (one entry "
+                             "per document)")
+        if isinstance(n_groups, bool) or not isinstance(n_groups, (int, np.integer)):
+            raise ValueError("n_groups must be an int")
+        G = int(n_groups)
+        if G < 0 or G > np.iinfo(np.int32).max:
+            raise ValueError(f"n_groups = {G} must be in 0 .. 2^31 - 1")
+        if (d_groups is None) != (G == 0):
+            raise ValueError("d_groups and n_groups come together (d_groups=None with "
+                             "n_groups=0: one bucket per mask)")
+        if d_groups is not None and (
+                d_groups.dim() != 1 or d_groups.shape[0] != self.n_docs
+                or d_groups.dtype != torch.int32 or not d_groups.is_contiguous()):
+            raise ValueError(f"d_groups must be an int32 [{self.n_docs}] tensor (one group per "
+                             "document)")
+        B = G or 1
+        sum_dtype = torch.float64 if d_values.dtype == torch.float32 else torch.int64
+        for name, t, dt, need in (("d_count", d_count, torch.int64, True),
+                                  ("d_min", d_min, d_values.dtype, False),
+                                  ("d_max", d_max, d_values.dtype, False),
+                                  ("d_sum", d_sum, sum_dtype, False)):
+            if t is None and not need:
+                continue
+            if (t is None or t.dim() != 2 or tuple(t.shape) != (M, B) or t.dtype != dt
+                    or not t.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous {dt} [{M}, {B}] tensor (one row "
+                                 "per mask)")
+        kind = kinds[d_values.dtype]
+        need = 8 * M * B * (36 if kind == 1 else 4)
+        s = _stream(stream)
+        if d_scratch is None:
+            # allocated on the call's stream, so the allocator hands the block
+            # on only after the kernels enqueued here
+            dev = d_masks.device
+            ts = torch.cuda.ExternalStream(s, device=dev) if s else torch.cuda.default_stream(dev)
+            with torch.cuda.stream(ts):
+                d_scratch = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
+        nbytes = d_scratch.numel() * d_scratch.element_size()
+        if not d_scratch.is_contiguous() or nbytes < need or d_scratch.data_ptr() % 8:
+            raise ValueError(f"d_scratch must be a contiguous, 8-byte aligned tensor of at least "
+                             f"{need} bytes (stats_scratch_bytes)")
+        p = lambda t, n: ctypes.c_void_p(t.data_ptr()) if t is not None and n else None
+        pg = None if d_groups is None else ctypes.c_void_p(d_groups.data_ptr() or 8)
+        check(lib.bm25_mask_stats_device(
+            self._h, p(d_masks, M and W), M, p(d_values, self.n_docs), kind, pg, G,
+            p(d_count, M), p(d_min, M), p(d_max, M), p(d_sum, M),
+            ctypes.c_void_p(d_scratch.data_ptr()), nbytes, ctypes.c_void_p(s)))
 
     def range_masks(self, values, fields, lo, hi, base=None) -> np.ndarray:
         """Allow-masks of numeric range filters (bm25_range_masks, host arrays)

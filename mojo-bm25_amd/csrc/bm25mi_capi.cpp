@@ -1716,6 +1716,93 @@ int bm25_mask_facets_device(bm25_index* h, const uint32_t* d_masks, int64_t M,
   return BM25_OK;
 }
 
+int bm25_mask_stats_scratch(const bm25_index* h, int32_t kind, int64_t M, int64_t G,
+                            int64_t* bytes) {
+  if (!h) return fail(BM25_EINVAL, "NULL index");
+  int rc = check_kind(kind);
+  if (!rc) rc = check_facet_shape(M, G);
+  if (rc) return rc;
+  if (!bytes) return fail(BM25_EINVAL, "NULL output");
+  const int64_t b = stats_scratch_bytes(kind, M, G);
+  if (b < 0)
+    return fail(BM25_EINVAL, "M = %lld rows of %lld buckets: the scratch does not fit int64 bytes",
+                (long long)M, (long long)(G > 0 ? G : 1));
+  *bytes = b;
+  return BM25_OK;
+}
+
+int bm25_mask_stats(bm25_index* h, const uint32_t* masks, int64_t M, const void* values,
+                    int32_t kind, const int32_t* groups, int64_t G, int64_t* out_count,
+                    void* out_min, void* out_max, void* out_sum) {
+  int64_t bytes = 0;
+  int rc = bm25_mask_stats_scratch(h, kind, M, G, &bytes);
+  if (rc) return rc;
+  if ((groups == nullptr) != (G == 0))
+    return fail(BM25_EINVAL, "stats: groups and G come together (groups NULL with G = 0: one "
+                             "bucket per row)");
+  if (M == 0) return BM25_OK;
+  if (!out_count) return fail(BM25_EINVAL, "NULL output");
+  const int64_t n_docs = h->ix.n_docs, W = (n_docs + 31) >> 5, B = G > 0 ? G : 1;
+  if (W > 0 && !masks) return fail(BM25_EINVAL, "NULL masks");
+  if (n_docs > 0 && !values) return fail(BM25_EINVAL, "NULL values");
+  if (groups) {
+    rc = check_groups(groups, n_docs, G);
+    if (rc) return rc;
+  }
+  Enter in(h);
+  if (in.rc) return in.rc;
+  const int64_t es = (int64_t)field_bytes(kind);
+  HostCall c(h->stream);
+  const uint32_t* d_masks = c.upload(masks, M * W);
+  const char* d_values = c.upload((const char*)values, n_docs * es);
+  const int32_t* d_groups = groups ? c.upload(groups, n_docs) : nullptr;
+  // (with no document the groups are not read: any non-null pointer says "grouped")
+  if (groups && !d_groups) d_groups = c.alloc<int32_t>(1);
+  int64_t* d_count = c.alloc<int64_t>(M * B);
+  char* d_min = out_min ? c.alloc<char>(M * B * es) : nullptr;
+  char* d_max = out_max ? c.alloc<char>(M * B * es) : nullptr;
+  int64_t* d_sum = out_sum ? c.alloc<int64_t>(M * B) : nullptr;
+  char* d_scratch = c.alloc<char>(bytes);
+  if (c.ok())
+    c.run(launch_mask_stats(h->ix, d_masks, M, d_values, kind, d_groups, G, d_count, d_min, d_max,
+                            d_sum, d_scratch, h->stream));
+  c.download(out_count, d_count, M * B);
+  if (out_min) c.download((char*)out_min, d_min, M * B * es);
+  if (out_max) c.download((char*)out_max, d_max, M * B * es);
+  if (out_sum) c.download((int64_t*)out_sum, d_sum, M * B);  // (int64 or float64: 8 bytes)
+  return c.finish("mask_stats");
+}
+
+int bm25_mask_stats_device(bm25_index* h, const uint32_t* d_masks, int64_t M, const void* d_values,
+                           int32_t kind, const int32_t* d_groups, int64_t G, int64_t* d_count,
+                           void* d_min, void* d_max, void* d_sum, void* d_scratch,
+                           int64_t scratch_bytes, void* stream) {
+  int64_t bytes = 0;
+  const int rc = bm25_mask_stats_scratch(h, kind, M, G, &bytes);
+  if (rc) return rc;
+  if ((d_groups == nullptr) != (G == 0))
+    return fail(BM25_EINVAL, "stats: groups and G come together (groups NULL with G = 0: one "
+                             "bucket per row)");
+  if (M == 0) return BM25_OK;
+  if (!d_count) return fail(BM25_EINVAL, "NULL output");
+  if (h->ix.n_docs > 0 && !d_masks) return fail(BM25_EINVAL, "NULL masks");
+  if (h->ix.n_docs > 0 && !d_values) return fail(BM25_EINVAL, "NULL values");
+  if (!d_scratch) return fail(BM25_EINVAL, "NULL scratch");
+  if (scratch_bytes < bytes)
+    return fail(BM25_EINVAL, "scratch_bytes = %lld: bm25_mask_stats_scratch asks for %lld",
+                (long long)scratch_bytes, (long long)bytes);
+  if ((uintptr_t)d_scratch % 8)
+    return fail(BM25_EINVAL, "the scratch must be 8-byte aligned");
+  // reads the caller's buffers only (as bm25_mask_facets_device: no workspace,
+  // no index array, no ordering against the handle's searches)
+  Enter in(h);
+  if (in.rc) return in.rc;
+  HIP_TRY(launch_mask_stats(h->ix, d_masks, M, d_values, kind, d_groups, G, d_count, d_min, d_max,
+                            d_sum, d_scratch, (hipStream_t)stream),
+          "mask_stats launch");
+  return BM25_OK;
+}
+
 int bm25_search_boolean(bm25_index* h, const int32_t* queries, int64_t Q, int64_t T, int32_t k,
                         const int32_t* must, int64_t A, const int32_t* any, int64_t B,
                         const int32_t* must_not, int64_t N, const uint32_t* base, int64_t Mb,

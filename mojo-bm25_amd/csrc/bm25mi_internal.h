@@ -596,6 +596,44 @@ hipError_t launch_mask_facets(const DevIndex& ix, const uint32_t* d_masks, int64
                               const int32_t* d_groups, int64_t G, int64_t* d_counts,
                               hipStream_t stream);
 
+// Field statistics (bm25mi_stats.hip; bm25_mask_stats of include/bm25mi.h):
+// count, min, max and sum of d_values (kind: kField* below) over the documents
+// each row of d_masks[M][W] allows, per bucket: B = 1 bucket a row holding
+// every allowed document (d_groups null and G == 0), else B = G buckets by
+// d_groups[d] (an id outside [0, G) is in no bucket).  A float32 NaN is no
+// value.  Outputs [M][B], every entry written: d_count int64; d_min / d_max of
+// the column's type; d_sum int64 (integer kinds, wrapping) or float64 (the
+// exact sum rounded once, bm25mi_stats_sum.h); the last three may be null.
+// Bits at or past n_docs are ignored, no mask word at index >= W of a row and
+// no d_values / d_groups entry at index >= n_docs is read.  d_scratch:
+// stats_scratch_bytes(kind, M, G) bytes, 8-byte aligned — a record of
+// stats_slots(kind) u64 per bucket (count, ~min key, max key, sum or inf
+// counters, then the 32 float bins), cleared by the launch on its stream,
+// accumulated with integer atomics only and turned into the outputs by a
+// finalise kernel.  B <= stats_lds_buckets(kind): stats_rows(kind, B) rows
+// share one read of a chunk's column, their records in LDS; wider: a row per
+// item, global atomics.  A chunk is kStatsChunk documents on both routes.
+constexpr int64_t kStatsLdsSlots = 4608;   // u64 LDS slots of a workgroup (36 KiB)
+constexpr int64_t kStatsMaxRows = 64;      // mask rows of a row block, at most
+constexpr int64_t kStatsChunk = 8192;      // documents of a workgroup's chunk
+constexpr int64_t kStatsIntSlots = 4;      // count, ~min key, max key, sum
+constexpr int64_t kStatsF32Slots = 36;     // count, ~min key, max key, infs, 32 bins (288 B)
+inline int64_t stats_slots(int kind) { return kind == 1 ? kStatsF32Slots : kStatsIntSlots; }
+inline int64_t stats_lds_buckets(int kind) { return kStatsLdsSlots / stats_slots(kind); }
+inline int64_t stats_rows(int kind, int64_t B) {
+  return std::max<int64_t>(1, std::min<int64_t>(kStatsMaxRows, stats_lds_buckets(kind) / B));
+}
+// (-1: M * B records do not fit an int64 of bytes)
+inline int64_t stats_scratch_bytes(int kind, int64_t M, int64_t G) {
+  const int64_t B = G > 0 ? G : 1, rec = 8 * stats_slots(kind);
+  if (M > 0 && B > (int64_t)0x7FFFFFFFFFFFFFFFll / rec / M) return -1;
+  return std::max<int64_t>(M, 0) * B * rec;
+}
+hipError_t launch_mask_stats(const DevIndex& ix, const uint32_t* d_masks, int64_t M,
+                             const void* d_values, int kind, const int32_t* d_groups, int64_t G,
+                             int64_t* d_count, void* d_min, void* d_max, void* d_sum,
+                             void* d_scratch, hipStream_t stream);
+
 // Numeric range filters (bm25mi_range.hip): d_out[M][W] in the layout above,
 // row m = the documents d < n_docs that d_base allows ([Mb][W], Mb = 0 (null:
 // every document), 1 or M, exactly launch_term_masks' base) and whose fields
